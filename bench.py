@@ -9,7 +9,7 @@ before the timed region.  Default workload = BASELINE.json configs[1] (UR10 6-Do
 the other BASELINE configs (TIAGo 1e6, TALOS 4e6, human 1e7 streamed), by default with STRONG scaling: the config's total
 sample count is sharded over the GPUs (north_star: >= 6x at 8 GPUs on the sharded configs).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfgK] [--scaling weak|strong] [--samples S]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfgK] [--scaling weak|strong] [--samples S] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -215,7 +215,13 @@ def main():
     ap.add_argument("--host-wait", default=None, choices=["spin", "block"],
                     help="how the host waits for the GPU: spin (default for one GPU) or block = interrupt-driven (default "
                          "for several ranks on a node: spinning ranks can exhaust a container's CPU quota)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step of the headline workload returned (every "
+                         "numeric entry of IdentificationPipeline.run's result) as DIR/<name>.npy in float64 (rank 0); the "
+                         "inputs are seeded, so two builds run with the same arguments can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # the shipped library has no run-time switches; FIGH_LIB_PATH would swap in another build (tools/ A/B runs only)
     stray = sorted(k for k in os.environ if k.startswith("FIGH_"))
@@ -251,7 +257,7 @@ def main():
         if world > 1:
             group.barrier()
 
-    def measure(args, steps, warmup, with_cpu):
+    def measure(args, steps, warmup, with_cpu, dump_dir=None):
         """One BASELINE config measured on the ranks of this run: (line of rank 0 | None, structural result ok)."""
         fixture, model_name, n_config, chunk = CONFIGS[args.config]
         if args.chunk_samples and args.config == "cfg5":
@@ -327,6 +333,9 @@ def main():
         barrier()
         dt = time.perf_counter() - t0
         _lib.profile_enable(False)
+        if dump_dir is not None and rank == 0:
+            # (before the untimed passes below: they run the same pipeline again)
+            dump_outputs(out, dump_dir)
         dt_rank = dt
         if world > 1:
             dt = max(group.all_gather_object(dt))
@@ -622,7 +631,7 @@ def main():
         pipe = None  # (HBM back before the next config is set up)
         return (line if rank == 0 else None), ok
 
-    line, ok = measure(args, args.steps, args.warmup, not args.no_cpu_baseline)
+    line, ok = measure(args, args.steps, args.warmup, not args.no_cpu_baseline, dump_dir=args.dump_outputs)
     if args.strong_config and args.strong_config != args.config and ok:
         # north_star words its scaling target as STRONG scaling ("\u2265 6x at 8 GPUs"); the headline workload above is quoted
         # per GPU (weak).  So the same line carries a fixed-total-size measurement of a sharded BASELINE config (default
@@ -707,6 +716,30 @@ def spawn_ranks(n):
                 p.kill()
         raise
     return worst if worst >= 0 else 1
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out, path):
+    """The numeric entries of one pass's result (IdentificationPipeline.run: index lists, regrouping coefficients, column
+    norms, pivots, phi, ...) as path/<key>.npy in float64; the expression strings are left out.  Every entry is a few
+    hundred numbers at most (they scale with the column count, not the samples), so nothing needs to be sampled.
+    Two runs agree up to rounding, not bit for bit, in what comes from the triangle (absdiagR, phi_ls, residual_norm):
+    which consumer wave factors which tile is decided at run time (the fused launch)."""
+    arrays = {}
+    for key, val in sorted(out.items()):
+        if val is None or isinstance(val, str):
+            continue
+        arr = np.asarray(val)
+        if arr.dtype.kind in "biuf":
+            arrays[key] = np.array(arr, dtype=np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py --dump-outputs: %d bytes of outputs, more than the %d allowed" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for key, arr in arrays.items():
+        np.save(os.path.join(path, key + ".npy"), arr)
 
 
 def meta_idx(meta):

@@ -28,6 +28,32 @@ def _free_port():
     raise RuntimeError("no free port pair")
 
 
+def _spawn(fn, args, nprocs):
+    """fn(rank, *args) in nprocs fresh processes, like torch.multiprocessing.spawn(join=True), without importing PyTorch
+    into the test process: once torch is loaded, its bundled HIP runtime and RCCL are the ones libfigh.so binds to in
+    every later test of the same session.  The first rank that exits non-zero ends the others and raises."""
+    import multiprocessing as mp
+    import time
+    ctx = mp.get_context("spawn")
+    procs = [ctx.Process(target=fn, args=(r,) + tuple(args)) for r in range(nprocs)]
+    for p in procs:
+        p.start()
+    try:
+        while any(p.exitcode is None for p in procs):
+            failed = [(r, p.exitcode) for r, p in enumerate(procs) if p.exitcode not in (None, 0)]
+            if failed:
+                raise RuntimeError("process %d terminated with exit code %d" % failed[0])
+            time.sleep(0.05)
+        failed = [(r, p.exitcode) for r, p in enumerate(procs) if p.exitcode != 0]
+        if failed:
+            raise RuntimeError("process %d terminated with exit code %d" % failed[0])
+    finally:
+        for p in procs:
+            if p.exitcode is None:
+                p.terminate()
+            p.join()
+
+
 def _worker(rank, world, port, out_dir):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     for p in (ROOT, os.path.join(ROOT, "oracle")):
@@ -66,9 +92,8 @@ def _worker(rank, world, port, out_dir):
 
 @pytest.mark.timeout(300)
 def test_two_rank_exchange_matches_single_process(tmp_path, oracle_lib):
-    import torch.multiprocessing as mp
     port = _free_port()
-    mp.spawn(_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
+    _spawn(_worker, (2, port, str(tmp_path)), 2)
     r0, r1 = np.load(tmp_path / "rank0.npz"), np.load(tmp_path / "rank1.npz")
     assert (int(r0["lo"]), int(r0["hi"]), int(r1["lo"]), int(r1["hi"])) == (0, 200, 200, 400)
     g = np.load(os.path.join(GOLD, "cfg2_ur10.npz"))
@@ -111,9 +136,8 @@ def test_two_rank_exchange_of_recorded_hip_triangles(tmp_path):
     by tools/record_hip_triangles.py: the level-0 + merge triangle of each of two sample shards, and the one-process
     triangle): the stack of the two device triangles reduces to the one-process device triangle (|R| to 1e-12), the rank
     decision on it is the golden base set."""
-    import torch.multiprocessing as mp
     port = _free_port()
-    mp.spawn(_hip_fixture_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
+    _spawn(_hip_fixture_worker, (2, port, str(tmp_path)), 2)
     r0, r1 = np.load(tmp_path / "rank0.npz")["R"], np.load(tmp_path / "rank1.npz")["R"]
     assert np.array_equal(r0, r1)
     z = np.load(os.path.join(GOLD, "hip_triangles_ur10.npz"))
@@ -169,7 +193,12 @@ def _setup_worker(rank, world, port, out_dir, scenario):
         raise RuntimeError("simulated: ncclGetUniqueId failed")
 
     fd.rccl_unique_id = unique_id
-    key = ("box", 0) if scenario == "shared_device" else None
+    if scenario == "shared_device":
+        key = ("box", 0)
+    elif scenario in ("id_fails", "init_fails", "init_local_failure"):
+        key = ("box", rank)  # one device per rank, whatever this host has: the set-up gets past phase 1 to the simulated failure
+    else:
+        key = None  # the real device of this host (no_device, rank1_fails)
     ex, info = fd.exchange_from_env("rccl", device_key=key)
     # the fallback exchange must work right away on every rank: no rank is stuck in another collective
     total = ex.allreduce_sum_host(np.array([float(rank + 1)]))
@@ -187,9 +216,8 @@ def test_rccl_setup_is_decided_collectively(tmp_path, scenario):
     preflight fails on one rank only; rank 0 fails to create the id after a clean preflight; two ranks name one device;
     and the real preflight of this GPU-less container."""
     import json
-    import torch.multiprocessing as mp
     port = _free_port()
-    mp.spawn(_setup_worker, args=(2, port, str(tmp_path), scenario), nprocs=2, join=True)
+    _spawn(_setup_worker, (2, port, str(tmp_path), scenario), 2)
     res = [json.load(open(tmp_path / ("rank%d.json" % r))) for r in range(2)]
     assert res[0]["collective"] == res[1]["collective"] and "host-staged" in res[0]["collective"]
     assert all(r["kind"] == "TorchExchange" and r["sum"] == 3.0 for r in res)
@@ -220,10 +248,9 @@ def test_shard_range_partitions():
 def test_rccl_local_setup_failure_fails_fast(tmp_path):
     """a rank that fails BEFORE joining ncclCommInitRank (its peers are blocked inside the rendezvous) must
     not wander off into a collective: it exits non-zero at once and the launcher tears the job down."""
-    import torch.multiprocessing as mp
     port = _free_port()
     with pytest.raises(Exception) as e:
-        mp.spawn(_setup_worker, args=(2, port, str(tmp_path), "init_local_failure"), nprocs=2, join=True)
+        _spawn(_setup_worker, (2, port, str(tmp_path), "init_local_failure"), 2)
     assert "exit code 3" in str(e.value) or "exitcode" in str(e.value).lower()
     assert not os.path.exists(tmp_path / "rank1.json")
 
