@@ -22,7 +22,8 @@
 //                         (figh_tsqr_narrow.h -- the code of the two-launch kernel, RLAST form: the last 16 columns of the
 //                         triangle in registers, 7.4 instead of 13.8 KB of LDS per wave).
 //
-// Measured on the first form (one producer, seven consumers with 13.8 KB triangles, tools/fused_prof.py): the producer needs
+// Measured on the first form (one producer, seven consumers with 13.8 KB triangles; in-kernel s_memtime buckets, an
+// instrumentation since removed): the producer needs
 // 10 000 cycles per tile (row emission 3 900, stream-out 2 000, column norms 1 600, forward recursion 1 100 -- a single wave
 // is latency-bound) where seven consumers finish a tile every 5 000, and everything that touches THE buffer is serial.
 // Hence two producers with a buffer each: 2 x 44 KB tiles + 2 x 9 KB staging + C x 7.4 KB triangles = 152 KB (C = 6).
@@ -41,19 +42,6 @@
 namespace figh {
 
 typedef double f64x2 __attribute__((ext_vector_type(2)));
-
-#ifdef FIGH_ABLATION
-// in-kernel time buckets (s_memtime ticks summed over all workgroups): producer [0] waiting for the buffer, [1] inputs +
-// forward recursion, [2] row emission, [3] stream-out, [4] column norms, [5] total; consumers [8] waiting for a tile,
-// [9] gather, [10] column steps, [11] total, [12] tiles
-__device__ unsigned long long g_fused_prof[16];
-__device__ int g_fused_opts = 0;  // 1: no column norms, 2: no stream-out, 4: no row emission arithmetic
-#define FUSED_TICK(var) const long long var = __builtin_readcyclecounter()
-#define FUSED_ADD(slot, dt) prof_##slot += (dt)
-#else
-#define FUSED_TICK(var)
-#define FUSED_ADD(slot, dt)
-#endif
 
 struct FusedCtrl {  // one per producer / tile buffer
     int produced;  // tiles announced so far (written by the producer only)
@@ -128,7 +116,6 @@ __global__ __launch_bounds__(512) void fused_chain_tsqr_kernel(
     for (int e = G::CONS0 + threadIdx.x; e < G::CONS0 + ncons * tri_doubles; e += blockDim.x) lds[e] = 0.0;
     __syncthreads();
 
-#ifndef FUSED_NO_PROD
     if (wave < G::NPROD) {
         // ================================================================================================== producers
         __builtin_amdgcn_s_setprio(3);
@@ -138,13 +125,7 @@ __global__ __launch_bounds__(512) void fused_chain_tsqr_kernel(
         double *my = tile + lane * LDT;
         double *stau = tile + G::TAU0, *sqd = tile + G::QD0, *cacc = tile + G::CS0;
         int t = 0;
-#ifdef FIGH_ABLATION
-        long long prof_0 = 0, prof_1 = 0, prof_2 = 0, prof_3 = 0, prof_4 = 0;
-        const int opts = g_fused_opts;
-        const long long prof_start = __builtin_readcyclecounter();
-#endif
         auto sample_tile = [&](auto FAST_T, const long s) {
-            FUSED_TICK(c0);
             constexpr bool FAST = decltype(FAST_T)::value;
             const long i0 = s * 64;
             const int nvalid = FAST ? 64 : (int)((N - i0) < 64 ? (N - i0) : 64);
@@ -219,8 +200,6 @@ __global__ __launch_bounds__(512) void fused_chain_tsqr_kernel(
                     }
                 }
             }
-            FUSED_TICK(c1);
-            FUSED_ADD(1, c1 - c0);
 #pragma unroll
             for (int jo = 0; jo < NJ; ++jo) {
                 // Row order 0, NJ-1, 1, NJ-2, ...: a row block of joint 1 costs a consumer ten times what one of joint 6 costs
@@ -229,13 +208,10 @@ __global__ __launch_bounds__(512) void fused_chain_tsqr_kernel(
                 const int j = (jo & 1) ? NJ - 1 - (jo >> 1) : (jo >> 1);
                 const int jprev = jo == 0 ? (((NJ - 1) & 1) ? NJ - 1 - ((NJ - 1) >> 1) : ((NJ - 1) >> 1))
                                           : (((jo - 1) & 1) ? NJ - 1 - ((jo - 1) >> 1) : ((jo - 1) >> 1));
-                FUSED_TICK(c2);
                 // the buffer is free once the previous tile has been gathered by its consumer (this wave's own reads of it
                 // -- stream-out, column norms -- are behind it in program order)
                 while (lds_peek(&ctrl->taken) < t) __builtin_amdgcn_s_sleep(1);
                 asm volatile("" ::: "memory");
-                FUSED_TICK(c3);
-                FUSED_ADD(0, c3 - c2);
                 // ---- this lane's row (j, i): 14 columns per link; links < j are structurally zero.  The buffer holds the row
                 // of joint jprev (zeros below 14 jprev, values from there on; the kernel's very first tile is row 0, which
                 // writes every column): only [14 jprev, 14 j) has to be cleared
@@ -301,18 +277,12 @@ __global__ __launch_bounds__(512) void fused_chain_tsqr_kernel(
                 my[NC] = tau ? stau[64 * j + lane] : 0.0;
                 lds_post(&ctrl->produced, t + 1);
                 ++t;
-                FUSED_TICK(c4);
-                FUSED_ADD(2, c4 - c3);
 
                 // ---- stream the 64 x NC tile to W rows j*N+i0 .. : one contiguous run (the launcher guarantees ldw == NC and
                 // 16-byte alignment).  Chunk id (16 B) sits at byte 16 id in W and at 16 (id + r) in the padded tile,
                 // r = id / CH by a magic multiply
                 double *dstW = W + ((long)j * N + i0) * NC;
                 const char *tbase = reinterpret_cast<const char *>(tile);
-#ifdef FIGH_ABLATION
-                if (opts & 2) {
-                } else
-#endif
                 if constexpr (FAST) {
                     // R rows per two passes of the wave, R = 128 / CH (UR10: three rows = 126 chunks of 16 B; seven links: two rows
                     // = 98): pass A takes slots 0..63 of the R rows, pass B slots 64..127 -- the slots behind R CH are the first
@@ -366,12 +336,7 @@ __global__ __launch_bounds__(512) void fused_chain_tsqr_kernel(
                         *reinterpret_cast<double2 *>(reinterpret_cast<char *>(dstW) + 16 * id) = val;
                     }
                 }
-                FUSED_TICK(c5);
-                FUSED_ADD(3, c5 - c4);
                 // ---- diag(W^T W): on joint row j the live columns are 14 j ..; lane owns 14 j + lane (and + 64)
-#ifdef FIGH_ABLATION
-                if (!(opts & 1))
-#endif
                 {
                     const int lo = 14 * j, width = NC - lo;
                     // RB rows requested at a time (the LDS latency is paid 64 / RB times per pass, not 64 times); sixteen where
@@ -400,8 +365,6 @@ __global__ __launch_bounds__(512) void fused_chain_tsqr_kernel(
                     if (lane < width) cacc[lo + lane] += column_sum(tile + lo + lane);
                     if (width > 64 && lane + 64 < width) cacc[lo + 64 + lane] += column_sum(tile + lo + 64 + lane);
                 }
-                FUSED_TICK(c6);
-                FUSED_ADD(4, c6 - c5);
             }
         };
         for (long s = b + wave * Gd; s < ntiles_s; s += G::NPROD * Gd) {
@@ -410,20 +373,8 @@ __global__ __launch_bounds__(512) void fused_chain_tsqr_kernel(
         }
         asm volatile("" ::: "memory");
         for (int c = lane; c < NC; c += 64) colsq_part[(b * G::NPROD + wave) * NC + c] = cacc[c];
-#ifdef FIGH_ABLATION
-        if (lane == 0) {
-            atomicAdd(&g_fused_prof[0], (unsigned long long)prof_0);
-            atomicAdd(&g_fused_prof[1], (unsigned long long)prof_1);
-            atomicAdd(&g_fused_prof[2], (unsigned long long)prof_2);
-            atomicAdd(&g_fused_prof[3], (unsigned long long)prof_3);
-            atomicAdd(&g_fused_prof[4], (unsigned long long)prof_4);
-            atomicAdd(&g_fused_prof[5], (unsigned long long)(__builtin_readcyclecounter() - prof_start));
-        }
-#endif
         return;
     }
-#endif
-#ifndef FUSED_NO_CONS
     // ======================================================================================================= consumers
     constexpr int LCH = NCC - 1;  // chunks of the triangle kept in LDS (RLAST form)
     const int c_id = wave - G::NPROD;
@@ -472,14 +423,9 @@ __global__ __launch_bounds__(512) void fused_chain_tsqr_kernel(
     FusedCtrl *ctrl0 = reinterpret_cast<FusedCtrl *>(lds + G::CTRL0);
     FusedCtrl *ctrl1 = reinterpret_cast<FusedCtrl *>(lds + G::PSIZE + G::CTRL0);
 
-#ifdef FIGH_ABLATION
-    long long prof_8 = 0, prof_9 = 0, prof_10 = 0, prof_12 = 0;
-    const long long prof_start = __builtin_readcyclecounter();
-#endif
     int pref = c_id & 1;  // the buffer this wave looks at first
     int absorbed = 0;     // tiles this wave has factored
     for (;;) {
-        FUSED_TICK(c0);
         // claim the next announced tile of either buffer (lane 0 decides, the wave follows): -1 = everything is claimed
         int pick = -2, tpick = 0;
         while (pick == -2) {
@@ -511,8 +457,6 @@ __global__ __launch_bounds__(512) void fused_chain_tsqr_kernel(
         if (pick < 0) break;
         pref = pick ^ 1;  // alternate between the buffers
         asm volatile("" ::: "memory");
-        FUSED_TICK(c1);
-        FUSED_ADD(8, c1 - c0);
         const double *tile = lds + pick * G::PSIZE;
         FusedCtrl *ctrl = pick ? ctrl1 : ctrl0;
         // row block of the tile: the producer's row order 0, NJ-1, 1, NJ-2, ...
@@ -539,24 +483,10 @@ __global__ __launch_bounds__(512) void fused_chain_tsqr_kernel(
 #pragma unroll
             for (int i = 0; i < RPL; ++i) asm volatile("" : "+v"(S.T[cc][i]));
         lds_post(&ctrl->taken, tpick + 1);
-        FUSED_TICK(c2);
-        FUSED_ADD(9, c2 - c1);
         S.null2 = absorbed * 64 < nc + 8 ? 0.0 : null2;  // (null pivots once the triangle is of full height: see tsqr2_level0_body)
         ++absorbed;
         tsqr2_panels<0, NCC, NRC, false, true>(S, first_nz, [](auto) {});
-        FUSED_TICK(c3);
-        FUSED_ADD(10, c3 - c2);
-        FUSED_ADD(12, 1);
     }
-#ifdef FIGH_ABLATION
-    if (lane == 0) {
-        atomicAdd(&g_fused_prof[8], (unsigned long long)prof_8);
-        atomicAdd(&g_fused_prof[9], (unsigned long long)prof_9);
-        atomicAdd(&g_fused_prof[10], (unsigned long long)prof_10);
-        atomicAdd(&g_fused_prof[11], (unsigned long long)(__builtin_readcyclecounter() - prof_start));
-        atomicAdd(&g_fused_prof[12], (unsigned long long)prof_12);
-    }
-#endif
     // this wave's triangle (compact nc x nc, row-major): the LDS chunks, then the register chunk
     double *Rg = Rws + ((long)b * ncons + c_id) * (long)nc * nc;
     const int nlds = 16 * LCH - pad;  // columns of the compact triangle that live in LDS
@@ -575,7 +505,6 @@ __global__ __launch_bounds__(512) void fused_chain_tsqr_kernel(
             if (k >= 0 && col >= k && col >= 0) Rg[(long)k * nc + col] = S.Rq[sl];
         }
     }
-#endif
 }
 
 // partial[b][c] -> out[c]: one workgroup per column, strided partial sums + LDS tree (fixed order: deterministic)
@@ -632,13 +561,6 @@ static int launch_fused(const figh_model_s *m, int flags, long N, const double *
     double *Rws = static_cast<double *>(workspace(sizeof(double) * (size_t)nc * nc * (grid * ncons + 1), 5));
     if (!part || !Rws) return FIGH_ERR_ALLOC;
     const ChainParams<NJ> P = chain_params<NJ>(m);
-#ifdef FIGH_ABLATION
-    {
-        const char *e = getenv("FIGH_FUSED_OPTS");
-        const int o = e ? atoi(e) : 0;
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_fused_opts), &o, sizeof(int));
-    }
-#endif
     {
         ProfileScope scope("fused_chain_tsqr", true);
         FIGH_LAUNCH_TIMED((fused_chain_tsqr_kernel<NJ>), dim3((unsigned)grid), dim3(64 * (G::NPROD + ncons)), lds, P, flags, N, q,
@@ -655,19 +577,6 @@ static int launch_fused(const figh_model_s *m, int flags, long N, const double *
 }  // namespace figh
 
 using namespace figh;
-
-#ifdef FIGH_ABLATION
-extern "C" int figh_fused_prof(double *out16, int reset) {
-    unsigned long long h[16];
-    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_fused_prof), sizeof(h)) != hipSuccess) return FIGH_ERR_NO_DEVICE;
-    for (int i = 0; i < 16; ++i) out16[i] = (double)h[i];
-    if (reset) {
-        unsigned long long z[16] = {};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_fused_prof), z, sizeof(z));
-    }
-    return FIGH_OK;
-}
-#endif
 
 extern "C" int figh_regressor_tsqr_fused(figh_model_t model, int flags, int64_t N, const double *d_q, const double *d_v,
                                          const double *d_a, double *d_W, int64_t ldw, double *d_colsq,

@@ -476,10 +476,7 @@ static int tsqr_level(const double *W, long rows, long ldw, const int *col_idx, 
     const int *th = hint ? hint : zero_tile_hint(ntiles);
     if (!th) return FIGH_ERR_ALLOC;
     dim3 grid((unsigned)nw), block(64);
-    bool tall48 = nc > 64 && !hint && rows >= 6L * nc * cu_count() * 8;
-#ifdef FIGH_ABLATION
-    if (const char *e = getenv("FIGH_T53")) tall48 = nc > 64 && !hint && atoi(e) != 0;
-#endif
+    const bool tall48 = nc > 64 && !hint && rows >= 6L * nc * cu_count() * 8;
     if (nc <= 64)
         FIGH_LAUNCH_TIMED((tsqr2_kernel<4, 4, true>), grid, block, tsqr2_lds_bytes(4, nc), W, rows, ldw, col_idx, n, tau,
                           d_blkw, rows_per_blk, Rws_out, nc, th, null_pivot_sq());
@@ -713,12 +710,10 @@ int figh_tsqr_level0(const double *d_W, int64_t rows, int64_t ldw, const int32_t
     long target;
     if (nc <= 80) {
         // (65 .. 80 columns without a structure hint: the 48-row form with its register chunk, two waves per SIMD)
-        // -- when there are rows for eight waves per CU (same-box A/B in alternating order, tools/t53_ab.py: 3e6 x 77: 2.10-2.21
-        // against 2.30-2.45 ms, 1e6 x 66: 0.74 against 0.85-0.92 ms, 1e6 x 80: equal; 5e5 x 80: 0.59-0.61 against 0.53-0.75)
-        bool small_lds = nc > 64 && !g_tile_hint && rows >= 6L * nc * cu_count() * 8;
-#ifdef FIGH_ABLATION
-        if (const char *e = getenv("FIGH_T53")) small_lds = nc > 64 && !g_tile_hint && atoi(e) != 0;  // 1: always, 0: never
-#endif
+        // -- when there are rows for eight waves per CU (same-box A/B in alternating order, a probe since removed: 3e6 x 77:
+        // 2.10-2.21 against 2.30-2.45 ms, 1e6 x 66: 0.74 against 0.85-0.92 ms, 1e6 x 80: equal; 5e5 x 80: 0.59-0.61 against
+        // 0.53-0.75)
+        const bool small_lds = nc > 64 && !g_tile_hint && rows >= 6L * nc * cu_count() * 8;
         long per_cu = (long)((160 * 1024) / tsqr2_lds_bytes(nc <= 64 ? 4 : 5, nc, small_lds));
         if (per_cu > ((nc <= 64 || small_lds) ? 8 : 4)) per_cu = (nc <= 64 || small_lds) ? 8 : 4;
         if (per_cu < 1) per_cu = 1;

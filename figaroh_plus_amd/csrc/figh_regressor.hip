@@ -33,11 +33,6 @@
 namespace figh {
 
 // ---------------------------------------------------------------------------------------------- chain kernel
-#ifdef FIGH_ABLATION
-__device__ int g_chain_hotin = 0;
-__device__ int g_chain_blocked = 0;
-#endif
-
 // FIGAROH slot of Pinocchio inertia entry: [xx xy yy xz yz zz] -> Ixx Ixy Ixz Iyy Iyz Izz = slots 0 1 3 2 4 5
 template <int NJ, bool TX40, bool COLSQ>
 __global__ __launch_bounds__(64) void regressor_chain_kernel(const ChainParams<NJ> P, const int flags, const long N,
@@ -67,11 +62,7 @@ __global__ __launch_bounds__(64) void regressor_chain_kernel(const ChainParams<N
     auto fetch_inputs = [&](const long tile) {
         const long j0 = tile * 64;
         const int nv = (int)((N - j0) < 64 ? (N - j0) : 64);
-#ifdef FIGH_ABLATION
-        const long is = g_chain_hotin ? (lane < nv ? lane : nv - 1) : j0 + (lane < nv ? lane : nv - 1);
-#else
         const long is = j0 + (lane < nv ? lane : nv - 1);
-#endif
 #pragma unroll
         for (int k = 0; k < NJ; ++k) {
             pq[k] = q[is * NJ + k];
@@ -285,21 +276,13 @@ __global__ __launch_bounds__(64) void regressor_chain_kernel(const ChainParams<N
     // tile's NJ * CH stores.  Loads and stores retire through one in-order counter (vmcnt): a load issued BEHIND the stores
     // can only be waited for together with all of them, and the wave used to sit at the top of every tile until HBM had
     // acknowledged its last store and then delivered q, v, a (with the inputs served from cache the kernel is 0.065 ms
-    // faster, tools/k1_alloc_probe.py with FIGH_CHAIN_HOTIN).  Requested up front they are older than the stores, and
+    // faster, measured with a probe since removed).  Requested up front they are older than the stores, and
     // because this loop's body has a fixed number of stores on every path the compiler's wait for them is vmcnt(63):
     // all but the youngest 63 operations -- i.e. the stores of the last row block stay in flight.
     long t = blockIdx.x;
     if constexpr (G::VEC == 2) {
         const long nfast = (vec_ok && ldw == NC) ? N / 64 : 0;
-        long tstep = gridDim.x, tend = nfast;
-#ifdef FIGH_ABLATION
-        if (g_chain_blocked) {  // FIGH_K1_BLOCKED: every wave walks its own contiguous range of tiles (tools/k1_alloc_probe.py)
-            const long tpw = (nfast + gridDim.x - 1) / gridDim.x;
-            t = blockIdx.x * tpw;
-            tstep = 1;
-            tend = t + tpw < nfast ? t + tpw : nfast;
-        }
-#endif
+        const long tstep = gridDim.x, tend = nfast;
         if (t < tend) {
             fetch_inputs(t);
             // waited for here, outside the loop: a request still pending at the loop header would put a full wait at the
@@ -311,9 +294,6 @@ __global__ __launch_bounds__(64) void regressor_chain_kernel(const ChainParams<N
             const long tn = t + tstep;
             tile_body(std::true_type{}, t, tn < tend ? tn : t);
         }
-#ifdef FIGH_ABLATION
-        if (g_chain_blocked) t = nfast + blockIdx.x;
-#endif
     }
     for (; t < ntiles; t += gridDim.x) {
         fetch_inputs(t);
@@ -391,14 +371,6 @@ static int launch_chain(const figh_model_s *m, int flags, long N, const double *
     if (grid > ntiles) grid = ntiles;
     if (grid < 1) grid = 1;
     const int vec_ok = (ldw % G::VEC == 0) && ((reinterpret_cast<uintptr_t>(W) % (8 * G::VEC)) == 0);
-#ifdef FIGH_ABLATION
-    {
-        const int hot = getenv("FIGH_CHAIN_HOTIN") != nullptr;
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_chain_hotin), &hot, sizeof(int));
-        const int blk = getenv("FIGH_K1_BLOCKED") != nullptr;
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_chain_blocked), &blk, sizeof(int));
-    }
-#endif
     ProfileScope scope("regressor_chain", true);
     if (d_colsq) {
         double *part = static_cast<double *>(workspace(sizeof(double) * grid * G::NC, 0));

@@ -48,11 +48,9 @@
 #include "figh_spatial.h"
 #include "figh_wave.h"
 
-#ifndef FIGH_TREE_LSP
-#define FIGH_TREE_LSP 18  // LDS row stride of the segment tile in doubles (see regressor_tape_kernel)
-#endif
-
 namespace figh {
+
+constexpr int kTreeLsp = 18;  // LDS row stride of the segment tile in doubles (see regressor_tape_kernel)
 
 enum : int32_t { OP_RESET = 0, OP_STEP = 1, OP_EMIT = 2, OP_ZERO = 3, OP_TX40 = 4, OP_FETCH = 5, OP_RESTORE = 6 };
 // STEP flags (field b): bit 0 = the row's joint (J starts here), bits 4..6 = dof inside the joint (free-flyer),
@@ -79,11 +77,6 @@ struct TapeOp {
 
 namespace {
 
-#ifdef FIGH_ABLATION
-__device__ int g_tree_hotin = 0;
-__device__ int g_tree_half = 0;  // FIGH_TREE_HALF: force rows store only the upper 64 bytes of every line (timing probe)
-#endif
-
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // Stream one link segment -- the tile, 64 rows x LS doubles -- to rows rowbase .. + nvalid - 1, columns col0 .. col0 + LS - 1
@@ -97,7 +90,7 @@ __device__ __forceinline__ void flush_tile(const double *__restrict__ tile, doub
                                            const bool skip_lo = false, const int col0_acc = -1,
                                            const bool nostore = false, const int force_pos0 = -1) {
     constexpr int CP = LS / 2, RPI = 64 / CP;  // 16-byte chunks per row, rows per store instruction
-    constexpr int LSP = FIGH_TREE_LSP;         // LDS row stride of the tile (see regressor_tape_kernel)
+    constexpr int LSP = kTreeLsp;         // LDS row stride of the tile (see regressor_tape_kernel)
     const int rg = lane / CP, ch = lane - rg * CP;
     const bool active = rg < RPI;
     // (acc0, acc1: this lane's column pair, summed over its rows -- and, external-wrench mode, over the six row blocks of the
@@ -218,7 +211,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FC ? 1 : 2))
     // per segment, and the flush's ds_read_b128 (8 rows x 8 chunks per instruction) 8-way on top: the kernel spent its time
     // in LDS (TALOS: 198 segments per tile, ~1200 LDS cycles each = the whole 24 ms; a store-only tape ran 2.2 x faster).
     // 144 bytes (both segment widths): rows stay 16-byte aligned, eight consecutive rows cover all 32 banks.
-    constexpr int LSP = FIGH_TREE_LSP;
+    constexpr int LSP = kTreeLsp;
     double *tile = lds;            // 64 x LSP
     double *red = lds + 64 * LSP;  // 64 x 2
     double *colacc = red + 128;   // ncols_int (COLSQ): column sums in the kernel's own (LS-strided) numbering
@@ -243,17 +236,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FC ? 1 : 2))
         const long i = i0 + (lane < nvalid ? lane : nvalid - 1);
         // value k of this lane's sample is qi[k * is]: is = 1 for the reference's sample-major arrays, 64 for the
         // tile-blocked copies of figh_repack_samples (FIGH_FLAG_BLOCKED_INPUTS: the wave's 64 values of one k are one line)
-#ifdef FIGH_ABLATION
-        // FIGH_TREE_HOTIN: every tile reads the inputs of the first 64 samples (wrong numbers, same instruction stream):
-        // what the kernel would cost if q, v, a came from cache (tools/tree_hotin.sh)
-        const long iin = g_tree_hotin ? (lane < nvalid ? lane : nvalid - 1) : i;
-        const long tin = g_tree_hotin ? 0 : t;
-#else
-        const long iin = i, tin = t;
-#endif
-        const double *qi = blocked ? q + tin * 64 * nq + lane : q + iin * nq;
-        const double *vi = blocked ? v + tin * 64 * nv + lane : v + iin * nv;
-        const double *ai = blocked ? a + tin * 64 * nv + lane : a + iin * nv;
+        const double *qi = blocked ? q + t * 64 * nq + lane : q + i * nq;
+        const double *vi = blocked ? v + t * 64 * nv + lane : v + i * nv;
+        const double *ai = blocked ? a + t * 64 * nv + lane : a + i * nv;
         // state of the current link
         double V[6] = {0, 0, 0, 0, 0, 0}, A[6] = {-g0, -g1, -g2, 0, 0, 0};
         double Rc[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, pc[3] = {0, 0, 0};  // EXTFF: link -> root-joint frame
@@ -574,13 +559,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FC ? 1 : 2))
                                                          8u * (unsigned)ldc, i0, (od & 0xffff) - 1, cs0, cs1, fold, false, col0,
                                                          (oc & EMIT_NOSTORE) != 0);
                         } else {
-#ifdef FIGH_ABLATION
-                            flush_tile<LS, STORE, COLSQ>(tile, red, colacc, lane, nvalid, Wseg, ldw, ldw8, rowbase, col0, cs0, cs1, fold,
-                                                         EXTFF && g_tree_half && c < 3);
-#else
                             flush_tile<LS, STORE, COLSQ>(tile, red, colacc, lane, nvalid, Wseg, ldw, ldw8, rowbase, col0, cs0, cs1, fold,
                                                          false, -1, !EXTFF && (oc & EMIT_NOSTORE) != 0);
-#endif
                         }
                     } else if (!(oc & EMIT_NOSTORE)) {  // odd column count / unaligned W: plain 8-byte stores, no fused norms
                         for (int id = lane; id < nvalid * 14; id += 64) {
@@ -1038,30 +1018,6 @@ int launch_regressor_tree(const figh_model_s *m, int mode, int flags, int ft_mas
                                         : (mode == FIGH_MODE_JOINT_TORQUE && h.nv == h.njoints - 1
                                                ? build_tape_torque_rows(h, flags, ls, m->active_rows)
                                                : build_tape_rows(h, mode, flags, ft_mask, ls, m->active_rows));
-#ifdef FIGH_ABLATION
-        {
-            const int hot = getenv("FIGH_TREE_HOTIN") != nullptr;
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(g_tree_hotin), &hot, sizeof(int));
-            const int half = getenv("FIGH_TREE_HALF") != nullptr;
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(g_tree_half), &half, sizeof(int));
-        }
-        if (const char *e = getenv("FIGH_TREE_TAPE")) {  // store-pattern ceilings: W is all zeros, timing only
-            TapeBuilder T(h);
-            const int nrows = mode == FIGH_MODE_EXT_WRENCH ? 6 : h.nv;
-            if (!strncmp(e, "zrun", 4)) {  // runs of k links, row-block-major
-                const int k = atoi(e + 4);
-                for (int r = 0; r < nrows; ++r)
-                    for (int b = 1; b <= h.nlinks; b += k)
-                        T.zero(r, ls * (b - 1), ls * (b + k - 1 <= h.nlinks ? k : h.nlinks - b + 1));
-            } else if (!strcmp(e, "zlink")) {  // one segment per (link, row block), link-major
-                for (int b = 1; b <= h.nlinks; ++b)
-                    for (int r = 0; r < nrows; ++r) T.zero(r, ls * (b - 1), ls);
-            } else {  // whole rows
-                for (int r = 0; r < nrows; ++r) T.zero(r, 0, ncols_int);
-            }
-            ops = T.ops;
-        }
-#endif
         DeviceTape dt;
         dt.n = (int)ops.size();
         dt.extff = extff;
@@ -1091,11 +1047,8 @@ int launch_regressor_tree(const figh_model_s *m, int mode, int flags, int ft_mas
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     // (force-compact: the norm fold of a partial last group of links touches up to 3 x 16 entries behind the last column)
-    const size_t lds = sizeof(double) * (64 * (size_t)FIGH_TREE_LSP + 128 + (size_t)(fuse ? ncols_int + (fc ? 64 : 0) : 0));
+    const size_t lds = sizeof(double) * (64 * (size_t)kTreeLsp + 128 + (size_t)(fuse ? ncols_int + (fc ? 64 : 0) : 0));
     long grid = (long)cus * 8;
-#ifdef FIGH_ABLATION
-    if (const char *e = getenv("FIGH_TREE_WAVES")) grid = (long)cus * atoi(e);
-#endif
     if (grid > ntiles) grid = ntiles;
     if (grid < 1) grid = 1;
     double *part = nullptr;

@@ -198,11 +198,7 @@ static int regressor_tsqr_impl(figh_model_t model, int mode, int flags, int ft_m
     // triangle across the chunks (same workgroup count in every launch; a launch starts from the triangle the previous one
     // wrote), so the stack to merge holds one launch's triangles instead of nchunks times as many (human model, 20 chunks:
     // 512 instead of 10 240 triangles, merges 8.3 -> 1.8 ms).
-#ifdef FIGH_ABLATION
-    const bool chained = nc > 80 && nchunks > 1 && !getenv("FIGH_NO_CHAIN");  // same-box A/B (tools/chain_ab.sh)
-#else
     const bool chained = nc > 80 && nchunks > 1;
-#endif
     // External wrench on a free-flyer root: per chunk the three force row blocks are factored over the nf columns that can
     // be non-zero there (rotational-inertia columns are exact zeros in force rows, figh_tsqr_selected_wrench) and reduced to
     // one triangle per chunk; the torque row blocks go through the (chained) launches over all columns.

@@ -31,26 +31,11 @@
 
 namespace figh {
 
-#ifdef FIGH_ABLATION
-// in-kernel step profile of the ablation build (tools/stream_prof.py): s_memtime at five points of every column step of
-// wave 0 of workgroup 0, accumulated per point
-__device__ long long g_stream_prof[8];
-#define FIGH_PROF_MARK(i) \
-    if (blockIdx.x == 0 && threadIdx.x == 0) { const long long now_ = (long long)__builtin_readcyclecounter(); g_stream_prof[i] += now_ - prof_t; prof_t = now_; }
-#define FIGH_PROF_BEGIN long long prof_t = (long long)__builtin_readcyclecounter();
-#else
-#define FIGH_PROF_MARK(i)
-#define FIGH_PROF_BEGIN
-#endif
-
 constexpr unsigned long long kPoison = 0xFFFBADC0FFEE5EEDull;
 // how many column steps ahead a row is requested.  Measured (tools/merge_tree_bench.py, 2039 triangles of 50 columns):
 // depth 1 / 2 / 3 / 4 -> 107 / 117 / 124 / 129 us: a deeper request only adds lag per level, the step itself does not wait
 // for its loads
-#ifndef FIGH_STREAM_DEPTH
-#define FIGH_STREAM_DEPTH 1
-#endif
-constexpr int kDepth = FIGH_STREAM_DEPTH;
+constexpr int kDepth = 1;
 
 struct StreamPlan {
     int nlevels;   // merge levels; 0: `in` already is the plain triangle (regrouping only)
@@ -140,7 +125,6 @@ __device__ __forceinline__ void stream_step(double (&T)[merge_tile_n(NCC, FANR)]
     constexpr int kpos = 16 * P + KK;
     constexpr int J = kpos / 8, OW = kpos % 8;  // slot and owner wave of the arriving position
     const int buf = kpos & 1;
-    FIGH_PROF_BEGIN
     // the rows of position kpos + kDepth are requested now by the wave that owns them (its slot is not read before then)
     if constexpr (kpos + kDepth < 16 * NCC) {
         if (c.wave == (kpos + kDepth) % 8) arrive_issue<kpos + kDepth, NCC, FANR>(T, c);
@@ -149,7 +133,6 @@ __device__ __forceinline__ void stream_step(double (&T)[merge_tile_n(NCC, FANR)]
         if (kpos - c.pad < kDepth) arrive_issue<kpos, NCC, FANR>(T, c);  // the first steps: nobody asked before
         arrive_validate<kpos, NCC, FANR>(T, c);
     }
-    FIGH_PROF_MARK(0)
     const bool own = c.wave <= OW;  // this wave's slot J has arrived (position wave + 8 J <= kpos)
     double a0[LIVE], a1[LIVE];
 #pragma unroll
@@ -178,9 +161,7 @@ __device__ __forceinline__ void stream_step(double (&T)[merge_tile_n(NCC, FANR)]
         const double dw = allreduce_rowgroups(a0[cc] + a1[cc]);
         if (c.lane_g == 0) pw[buf][c.wave][16 * (P + cc) + c.lane_c] = dw;
     }
-    FIGH_PROF_MARK(1)
     __syncthreads();
-    FIGH_PROF_MARK(2)
     // every wave sums the partials itself, in wave order: same bits everywhere.  Pivot chunk first: it feeds the
     // rsq chain, behind which the reads of the trailing chunks hide.
     double d[LIVE];
@@ -201,10 +182,6 @@ __device__ __forceinline__ void stream_step(double (&T)[merge_tile_n(NCC, FANR)]
     }
     rs = sigma != 0.0 ? rs : 0.0;  // zero column: H = I and a row of zeros (which must still be published)
     const int k = kpos - c.pad;
-#ifdef FIGH_ABLATION
-    asm volatile("" : "+v"(rs));
-#endif
-    FIGH_PROF_MARK(3)
 #pragma unroll
     for (int cc = LIVE - 1; cc >= 0; --cc) {
         const double wj = d[cc] * rs;
@@ -224,7 +201,6 @@ __device__ __forceinline__ void stream_step(double (&T)[merge_tile_n(NCC, FANR)]
             if (c.plain) c.plain[(unsigned)(k * c.nc + col)] = val;
         }
     }
-    FIGH_PROF_MARK(4)
 }
 
 template <int P, int NCC, int FANR, int NW>
@@ -509,11 +485,3 @@ int launch_tsqr_stream(const double *Rs, long count, int nc, int n_free, double 
 
 }  // namespace figh
 
-#ifdef FIGH_ABLATION
-extern "C" int figh_ab_stream_prof(long long *h_out, int reset) {
-    long long zero[8] = {0};
-    if (hipMemcpyFromSymbol(h_out, HIP_SYMBOL(figh::g_stream_prof), sizeof(zero)) != hipSuccess) return -1;
-    if (reset && hipMemcpyToSymbol(HIP_SYMBOL(figh::g_stream_prof), zero, sizeof(zero)) != hipSuccess) return -1;
-    return 0;
-}
-#endif

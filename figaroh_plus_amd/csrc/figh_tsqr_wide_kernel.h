@@ -49,28 +49,6 @@ namespace figh {
 
 namespace {
 
-// in-kernel s_memtime accounting, ablation build only (FIGH_WY_PROF=1): per wave {kernel, tile top, first panel,
-// look-ahead chunk update, look-ahead panel, trailing updates, barrier waits}
-#ifdef FIGH_ABLATION
-#define FIGH_PROF_DECL long long pc_[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; long long pt_ = __builtin_readcyclecounter(); const long long pbegin_ = pt_;
-#define FIGH_PROF_ADD(k) do { const long long now_ = __builtin_readcyclecounter(); pc_[k] += now_ - pt_; pt_ = now_; } while (0)
-#define FIGH_PROF_STORE(ptr, w, nw) do { if ((ptr) && lane == 0) { pc_[0] = __builtin_readcyclecounter() - pbegin_; for (int k_ = 0; k_ < 12; ++k_) (ptr)[((long)blockIdx.x * (nw) + (w)) * 12 + k_] = pc_[k_]; } } while (0)
-#else
-#define FIGH_PROF_DECL
-#define FIGH_PROF_ADD(k) do {} while (0)
-#define FIGH_PROF_STORE(ptr, w, nw) do {} while (0)
-#endif
-
-#ifdef FIGH_ABLATION
-__device__ int g_wy_ralias = 0;
-__device__ int g_wy_off = 0;  // FIGH_WY_OFF: wave relabelling per workgroup (which SIMD hosts the owner of panel p)
-__device__ int g_wy_delay_mode = 0, g_wy_delay_ticks = 0;  // FIGH_WY_DELAY="mode,ticks": start-up delay of some workgroups
-#endif
-
-#ifndef FIGH_WY_TMODE
-#define FIGH_WY_TMODE 0  // where T is formed: see wy_panel_step (0: inside the column steps; 2: once per panel -- measured in round 6, not faster)
-#endif
-
 constexpr int kLdv = 17;  // LDS row stride of V (doubles): the transposed reads of B -= V Wm hit 16 different banks
 
 constexpr int kLdt = 17;  // LDS row stride of T (doubles): T[row][col] at row * kLdt + col
@@ -97,24 +75,16 @@ struct TColumn<M1, M1> {
     static __device__ __forceinline__ void dot(double &, double &, const double (&)[8], const double) {}
 };
 
-#ifdef FIGH_WY_LDSRED
-#define FIGH_WY_REDUCE(red, lane, x) allreduce_rowgroups_lds(red, lane, x)
-#else
-#define FIGH_WY_REDUCE(red, lane, x) allreduce_rowgroups(x)
-#endif
-
 // One column step of a panel.  X = the panel's chunk (lane (g, c): rows 16 rc + 4 r + g of column c, i = 4 rc + r),
 // Rl = the 16 x 16 diagonal block in wave-private LDS (row-major), Tl = the T factor being built (LDS, zero-filled),
 // myinv = 1 / (alpha - beta) of reflector c (0 until column c has been factored).  Columns c < KK are finished
 // reflectors and stay frozen (they are V, up to the scaling by myinv).
-// TMODE (round 6): 0 = column KK of T is formed INSIDE the step (larft forward, as described above: 15 DPP FMAs + the LDS
-// reads of T's row per step -- 106 of a step's 753 ticks, tools/microbench/step_bench.hip); 2 = the step only leaves the Gram
-// entries v_m^T v_KK (m < KK) and tau_KK in column KK of the T buffer and wy_larft_rows turns the buffer into T once per panel;
-// 1 = Gram entries only, no T at all (microbenchmark: the bound on what 2 can gain).
-template <int KK, int RPL, int TMODE = 0>
+// Column KK of T is formed INSIDE the step (larft forward, as described above: 15 DPP FMAs + the LDS reads of T's row per
+// step -- 106 of a step's 753 ticks, tools/microbench/step_bench.hip).  Forming T once per panel from the Gram entries instead
+// was measured in round 6 and is not faster (profiles/r06_larft_placement_ab.txt; the knob was removed).
+template <int KK, int RPL>
 __device__ __forceinline__ void wy_panel_step(double (&X)[RPL], double &myinv, double *__restrict__ Rl,
-                                              double *__restrict__ Tl, double *__restrict__ red, const int lane,
-                                              const int c_, const double null2) {
+                                              double *__restrict__ Tl, const int lane, const int c_, const double null2) {
     // (the lane's column, opaque per step: the comparisons with KK below are then two v_cmp here -- hoisted out of the sixteen
     // steps they become 32 lane masks in SGPR pairs that the allocator parks in VGPR lanes and fetches back with four
     // v_readlane per step)
@@ -123,7 +93,7 @@ __device__ __forceinline__ void wy_panel_step(double (&X)[RPL], double &myinv, d
     double rk = Rl[KK * 16 + c];  // row KK of the diagonal block: requested before the dot products
     constexpr int KH = KK < 8 ? KK : 8;
     double tr[8];
-    if constexpr (TMODE == 0) TColumn<0, KH>::load(tr, Tl + c * kLdt);
+    TColumn<0, KH>::load(tr, Tl + c * kLdt);
     double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
 #pragma unroll
     for (int i = 0; i < RPL; i += 4) {
@@ -132,7 +102,7 @@ __device__ __forceinline__ void wy_panel_step(double (&X)[RPL], double &myinv, d
         fmac_bcast<KK>(s2, X[i + 2], X[i + 2]);
         fmac_bcast<KK>(s3, X[i + 3], X[i + 3]);
     }
-    const double d = FIGH_WY_REDUCE(red, lane, (s0 + s1) + (s2 + s3));  // x^T X[:, c], identical in all row groups
+    const double d = allreduce_rowgroups((s0 + s1) + (s2 + s3));  // x^T X[:, c], identical in all row groups
     asm volatile("" : "+v"(rk));
     const double sigma = row_bcast<KK>(d);
     const double alpha = row_bcast<KK>(rk);
@@ -146,12 +116,10 @@ __device__ __forceinline__ void wy_panel_step(double (&X)[RPL], double &myinv, d
     double vg = d * myinv;
     asm volatile("s_nop 1" : "+v"(vg));  // VALU write -> DPP read of vg below: 2 wait states
     double acc0 = 0.0, acc1 = 0.0;
-    if constexpr (TMODE == 0) {
-        TColumn<0, KH>::dot(acc0, acc1, tr, vg);
-        if constexpr (KK > 8) {
-            TColumn<8, KK>::load(tr, Tl + c * kLdt);
-            TColumn<8, KK>::dot(acc0, acc1, tr, vg);
-        }
+    TColumn<0, KH>::dot(acc0, acc1, tr, vg);
+    if constexpr (KK > 8) {
+        TColumn<8, KK>::load(tr, Tl + c * kLdt);
+        TColumn<8, KK>::dot(acc0, acc1, tr, vg);
     }
     // (round 5: the reciprocal of the scalars runs beside the rsq correction, householder_scalars4; starting the whole chain
     // in front of the test -- as the register-tile step now does -- costs this kernel 12 .. 16 more bytes of scratch in the
@@ -168,8 +136,7 @@ __device__ __forceinline__ void wy_panel_step(double (&X)[RPL], double &myinv, d
     // sum of T's row entries is zero by itself for c >= KK (T is upper triangular, vg is zero there)
     if (lane < 16) {
         Rl[KK * 16 + c] = rk - wj;
-        if constexpr (TMODE == 0) Tl[c * kLdt + KK] = fma(-tfac * inv, acc0 + acc1, (c == KK) ? tfac : 0.0);
-        else Tl[c * kLdt + KK] = (c == KK) ? tfac : vg * inv;  // v_c^T v_KK for c < KK (vg is zero from the diagonal on), tau_KK
+        Tl[c * kLdt + KK] = fma(-tfac * inv, acc0 + acc1, (c == KK) ? tfac : 0.0);
     }
     myinv = (c == KK) ? inv : myinv;
     // the next step reads X through DPP operands of inline asm, which the hazard recognizer cannot see: nothing of it
@@ -177,59 +144,12 @@ __device__ __forceinline__ void wy_panel_step(double (&X)[RPL], double &myinv, d
     __builtin_amdgcn_sched_barrier(0);
 }
 
-template <int M, int K>
-struct LarftAxpy {  // Tr[k] += S[M][k] Tr[M] for k = K .. 15: independent FMAs, S[M][k] = lane-column M of the loaded column k
-    static __device__ __forceinline__ void run(const double (&col)[16], double (&Tr)[16]) {
-        if constexpr (K < 16) {
-            fmac_bcast<M>(Tr[K], col[K], Tr[M]);
-            LarftAxpy<M, K + 1>::run(col, Tr);
-        }
-    }
-};
-// right-looking: once T[r][M] is final it is added into every later column's sum at once -- the dependent chain is sixteen
-// short links (finalise, one FMA), not the 120 FMAs of the row-by-row dot products (measured: 2000 against 1900 ticks saved)
-template <int M>
-__device__ __forceinline__ void larft_row(const double (&col)[16], double (&Tr)[16], const int c) {
-    const double tau = row_bcast<M>(col[M]);
-    Tr[M] = (c == M) ? tau : -tau * Tr[M];
-    if constexpr (M < 15) {
-        LarftAxpy<M, M + 1>::run(col, Tr);
-        larft_row<M + 1>(col, Tr, c);
-    }
-}
-
-// TMODE 2: the T buffer holds S = strict upper part of V^T V with tau on the diagonal (a null pivot left its column zero);
-// larft forward, T[r][k] = -tau_k sum_{m = r .. k-1} T[r][m] S[m][k], T[k][k] = tau_k, is a recurrence along each ROW: lane r keeps
-// its row of T in registers and takes S[m][k] from lane-column m of the loaded column k through the DPP operand of the FMA -- 120
-// FMAs per lane, once per panel, in place of 120 + the row reloads spread over the sixteen column steps.  Every row group
-// computes the same rows; the first one writes T back over S.
-__device__ __forceinline__ void wy_larft_rows(double *__restrict__ Tl, const int lane, const int c) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    double col[16], Tr[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) col[k] = Tl[c * kLdt + k];  // lane c: S[c][k] (c < k), tau_k (c == k), 0 (c > k)
-#pragma unroll
-    for (int k = 0; k < 16; ++k) asm volatile("" : "+v"(col[k]));
-    asm volatile("s_nop 1" ::: "memory");
-#pragma unroll
-    for (int k = 0; k < 16; ++k) Tr[k] = 0.0;
-    larft_row<0>(col, Tr, c);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();  // (every lane has its column entries before the first one is overwritten)
-    if (lane < 16) {
-#pragma unroll
-        for (int k = 0; k < 16; ++k) Tl[c * kLdt + k] = Tr[k];
-    }
-}
-
 // Factor one panel: on return Rl holds the new diagonal block, Vl (M x kLdv) the reflectors V = X diag(inv), Tl (16 x
 // kLdt, row-major) the T factor.
-template <int RPL, int TMODE = FIGH_WY_TMODE>
-__device__ __forceinline__ void wy_factor_panel(double (&X)[RPL], double *__restrict__ Rl, double *__restrict__ red,
-                                                double *__restrict__ Vl, double *__restrict__ Tl, const int lane,
-                                                const int c, const int g, const double null2) {
+template <int RPL>
+__device__ __forceinline__ void wy_factor_panel(double (&X)[RPL], double *__restrict__ Rl, double *__restrict__ Vl,
+                                                double *__restrict__ Tl, const int lane, const int c, const int g,
+                                                const double null2) {
     double myinv = 0.0;
     {
         // (a zero made HERE: hoisted out of the tile loop the constant lived in a register pair for the whole kernel, and the
@@ -248,22 +168,22 @@ __device__ __forceinline__ void wy_factor_panel(double (&X)[RPL], double *__rest
     for (int i = 0; i < RPL; ++i) asm volatile("" : "+v"(X[i]));
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
-    wy_panel_step<0, RPL, TMODE>(X, myinv, Rl, Tl, red, lane, c, null2);
-    wy_panel_step<1, RPL, TMODE>(X, myinv, Rl, Tl, red, lane, c, null2);
-    wy_panel_step<2, RPL, TMODE>(X, myinv, Rl, Tl, red, lane, c, null2);
-    wy_panel_step<3, RPL, TMODE>(X, myinv, Rl, Tl, red, lane, c, null2);
-    wy_panel_step<4, RPL, TMODE>(X, myinv, Rl, Tl, red, lane, c, null2);
-    wy_panel_step<5, RPL, TMODE>(X, myinv, Rl, Tl, red, lane, c, null2);
-    wy_panel_step<6, RPL, TMODE>(X, myinv, Rl, Tl, red, lane, c, null2);
-    wy_panel_step<7, RPL, TMODE>(X, myinv, Rl, Tl, red, lane, c, null2);
-    wy_panel_step<8, RPL, TMODE>(X, myinv, Rl, Tl, red, lane, c, null2);
-    wy_panel_step<9, RPL, TMODE>(X, myinv, Rl, Tl, red, lane, c, null2);
-    wy_panel_step<10, RPL, TMODE>(X, myinv, Rl, Tl, red, lane, c, null2);
-    wy_panel_step<11, RPL, TMODE>(X, myinv, Rl, Tl, red, lane, c, null2);
-    wy_panel_step<12, RPL, TMODE>(X, myinv, Rl, Tl, red, lane, c, null2);
-    wy_panel_step<13, RPL, TMODE>(X, myinv, Rl, Tl, red, lane, c, null2);
-    wy_panel_step<14, RPL, TMODE>(X, myinv, Rl, Tl, red, lane, c, null2);
-    wy_panel_step<15, RPL, TMODE>(X, myinv, Rl, Tl, red, lane, c, null2);
+    wy_panel_step<0, RPL>(X, myinv, Rl, Tl, lane, c, null2);
+    wy_panel_step<1, RPL>(X, myinv, Rl, Tl, lane, c, null2);
+    wy_panel_step<2, RPL>(X, myinv, Rl, Tl, lane, c, null2);
+    wy_panel_step<3, RPL>(X, myinv, Rl, Tl, lane, c, null2);
+    wy_panel_step<4, RPL>(X, myinv, Rl, Tl, lane, c, null2);
+    wy_panel_step<5, RPL>(X, myinv, Rl, Tl, lane, c, null2);
+    wy_panel_step<6, RPL>(X, myinv, Rl, Tl, lane, c, null2);
+    wy_panel_step<7, RPL>(X, myinv, Rl, Tl, lane, c, null2);
+    wy_panel_step<8, RPL>(X, myinv, Rl, Tl, lane, c, null2);
+    wy_panel_step<9, RPL>(X, myinv, Rl, Tl, lane, c, null2);
+    wy_panel_step<10, RPL>(X, myinv, Rl, Tl, lane, c, null2);
+    wy_panel_step<11, RPL>(X, myinv, Rl, Tl, lane, c, null2);
+    wy_panel_step<12, RPL>(X, myinv, Rl, Tl, lane, c, null2);
+    wy_panel_step<13, RPL>(X, myinv, Rl, Tl, lane, c, null2);
+    wy_panel_step<14, RPL>(X, myinv, Rl, Tl, lane, c, null2);
+    wy_panel_step<15, RPL>(X, myinv, Rl, Tl, lane, c, null2);
     // null pivots: the norm of what the column still holds below the triangle moves into R_kk (all sixteen lane-columns at
     // once; nothing to do for columns that formed a reflector or are exactly zero)
     if (null2 > 0.0) {
@@ -273,7 +193,7 @@ __device__ __forceinline__ void wy_factor_panel(double (&X)[RPL], double *__rest
             s0 = fma(X[i], X[i], s0);
             s1 = fma(X[i + 1], X[i + 1], s1);
         }
-        const double sc = FIGH_WY_REDUCE(red, lane, s0 + s1);
+        const double sc = allreduce_rowgroups(s0 + s1);
         if (lane < 16 && myinv == 0.0 && sc != 0.0) {
             const double r = Rl[c * 16 + c];
             const double q2 = fma(r, r, sc);
@@ -285,7 +205,6 @@ __device__ __forceinline__ void wy_factor_panel(double (&X)[RPL], double *__rest
     }
 #pragma unroll
     for (int i = 0; i < RPL; ++i) Vl[(16 * (i >> 2) + 4 * (i & 3) + g) * kLdv + c] = X[i] * myinv;
-    if constexpr (TMODE == 2) wy_larft_rows(Tl, lane, c);
 }
 
 // Apply the panel's block reflector to one trailing chunk B (NRC row chunks of 16 x 16, C/D layout) and to its block of
@@ -421,8 +340,8 @@ __global__ __launch_bounds__(64 * NW, WPE) void tsqr_wy_kernel(const double *__r
                                                                const int np_, const double *__restrict__ tau,
                                                                const double *__restrict__ blkw, const long rows_per_blk,
                                                                double *__restrict__ Rblkp_, double *__restrict__ Routp_,
-                                                               const int ncp_, long long *__restrict__ prof,
-                                                               const long pair_countp_, const int aux, const double null2_) {
+                                                               const int ncp_, const long pair_countp_, const int aux,
+                                                               const double null2_) {
     // MODE 0: level 0 (rows of one tall matrix, tiles dealt round-robin).  MODE 1 = PAIR, MODE 2 = BATCH, below.
     // MODE 4 = PAIR for several stacks at once (the wide row blocks of a tree's regressor, figh_tsqr_wide_pair.hip): Wp_ is
     // a device table of `aux` WyPairJob records; the workgroup looks up its job and is then a PAIR workgroup of that job.
@@ -467,44 +386,25 @@ __global__ __launch_bounds__(64 * NW, WPE) void tsqr_wy_kernel(const double *__r
     const long tstep = PAIR ? 1L : (BATCH ? pair_count : (long)gridDim.x);
     static_assert((NW & (NW - 1)) == 0 && NW >= 2, "NW must be a power of two >= 2");
     static_assert(CPW >= 2, "at least two chunk slots per wave");
-    FIGH_PROF_DECL
     if constexpr (WPE == 1) asm volatile("" ::: "a255");  // the allocation covers the SIMD: never two waves on one
     constexpr int RPL = 4 * NRC, M = 16 * NRC, VBUF = M * kLdv + 16 * kLdt, NQ = CPW - 1;
     constexpr bool kLateRetire = CPW <= 4 || LDSC;  // empirical, per geometry (same-box A/B)  // see the look-ahead block
     __shared__ double vt[3][VBUF];      // V (M x kLdv) followed by T (16 x kLdt); three buffers: panel p is still read in
                                         // phase p + 1 (deferred sweep of the wave that factored panel p + 1)
     __shared__ double rpp[NW][256];     // the diagonal block of the panel a wave is factoring (wave-private)
-    __shared__ double redbuf[NW][64];   // cross-row-group sums (wave-private)
     __shared__ int fnz[2][NW];
     __shared__ double lch[LDSC ? 16 * M : 8];
     const int lane = threadIdx.x & 63;
-#ifdef FIGH_ABLATION
-    // mode 1: workgroups of the second half of the grid rotated by two waves, 2: by one, 3: odd workgroups by two,
-    // 4: by blockIdx / 8 (the XCD-local index)
-    const int woff_ = g_wy_off == 1 ? (blockIdx.x >= gridDim.x / 2 ? 2 : 0)
-                      : g_wy_off == 2 ? (blockIdx.x >= gridDim.x / 2 ? 1 : 0)
-                      : g_wy_off == 3 ? ((blockIdx.x & 1) ? 2 : 0)
-                      : g_wy_off == 4 ? (int)(blockIdx.x >> 3) : 0;
-    const int wave = __builtin_amdgcn_readfirstlane(((threadIdx.x >> 6) + woff_) & (NW - 1));
-#else
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#endif
     const int c = lane & 15, g = lane >> 4;
     const int nch = (nc + 15) >> 4;
     constexpr int LC = NW * CPW;                               // the chunk that lives in LDS (LDSC)
     const int nreg = LDSC ? (nch < LC ? nch : LC) : nch;       // chunks held in register slots
     const bool lhave = LDSC && nch > LC;                       // the matrix reaches into the LDS chunk
     const bool lowner = lhave && wave == (LC & (NW - 1));      // the wave that looks after it
-#ifdef FIGH_ABLATION
-    // FIGH_WY_RALIAS: the workgroups of an XCD share ONE triangle (garbage results, same instruction stream): what the
-    // kernel would cost if the R blocks came from L2 instead of HBM / MALL
-    double *Rb = Rblk + (long)(g_wy_ralias ? (blockIdx.x & 7) : blockIdx.x) * ((long)nch * (nch + 1) / 2) * 256;
-#else
     double *Rb = Rblk + (long)bx * ((long)nch * (nch + 1) / 2) * 256;
-#endif
     auto block = [&](const int p, const int cc) { return Rb + ((long)cc * (cc + 1) / 2 + p) * 256; };
     double *Rl = rpp[wave];
-    double *red = redbuf[wave];
 
     // this wave's columns of the triangle start empty (pair-merge mode: as the workgroup's first triangle)
     auto init_block = [&](const int p, const int cc) {
@@ -521,11 +421,11 @@ __global__ __launch_bounds__(64 * NW, WPE) void tsqr_wy_kernel(const double *__r
     };
     // CHAIN (chained launches of a streamed run): the workgroup starts from its own triangle of the previous
     // sample chunk (read back from Rout) -- one RUNNING triangle per workgroup instead of one per workgroup and chunk (the
-    // human model's 20 chunks: 512 triangles to merge instead of 10 240).  Measured on one box (tools/chain_ab.sh): a launch
-    // that starts from a filled triangle takes 7.6 ms where one that starts from zeros takes 7.2 ms, whether the blocks are
-    // left in place or re-created, in or out of phase with the other workgroup of the CU (tools/wydelay_ab.sh) -- the
-    // operands of the first half of a launch (force rows: the inertia columns are exact zeros) are then no longer mostly
-    // zero; the merges saved (8.3 -> 1.8 ms) outweigh it.
+    // human model's 20 chunks: 512 triangles to merge instead of 10 240).  Measured on one box (a same-box A/B whose probe
+    // has since been removed): a launch that starts from a filled triangle takes 7.6 ms where one that starts from zeros
+    // takes 7.2 ms, whether the blocks are left in place or re-created, in or out of phase with the other workgroup of the
+    // CU -- the operands of the first half of a launch (force rows: the inertia columns are exact zeros) are then no
+    // longer mostly zero; the merges saved (8.3 -> 1.8 ms) outweigh it.
     if (lowner)
         for (int p = 0; p <= LC; ++p) init_block(p, LC);
 #pragma unroll
@@ -701,7 +601,6 @@ __global__ __launch_bounds__(64 * NW, WPE) void tsqr_wy_kernel(const double *__r
         for (int w = 1; w < NW; ++w) first_nz = min(first_nz, fnz[parity][w]);
         int p0 = __builtin_amdgcn_readfirstlane(first_nz) >> 4;
         if (p0 > nch) p0 = nch;
-        FIGH_PROF_ADD(1);
         long rn = r0n;
         asm volatile("" : "+s"(rn));
         // chunks in front of the first non-zero column take no part in this tile
@@ -730,10 +629,8 @@ __global__ __launch_bounds__(64 * NW, WPE) void tsqr_wy_kernel(const double *__r
                     }
                 }
                 FIGH_WY_WAVE_SYNC();
-                FIGH_PROF_ADD(8);
-                wy_factor_panel<RPL>(X, Rl, red, Vn, Vn + M * kLdv, lane, c, g, null2);
+                wy_factor_panel<RPL>(X, Rl, Vn, Vn + M * kLdv, lane, c, g, null2);
                 FIGH_WY_WAVE_SYNC();
-                FIGH_PROF_ADD(9);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) bpp[lane + 64 * r] = Rl[lane + 64 * r];
                 if constexpr (!kLateRetire) {
@@ -742,12 +639,8 @@ __global__ __launch_bounds__(64 * NW, WPE) void tsqr_wy_kernel(const double *__r
                 __builtin_amdgcn_s_setprio(0);
             }
             __syncthreads();
-            FIGH_PROF_ADD(2);
             if constexpr (kLateRetire) {
-                if (wave == (p0 & (NW - 1)) && !(LDSC && p0 == LC)) {
-                    FIGH_WY_RETIRE(rn);
-                    FIGH_PROF_ADD(10);
-                }
+                if (wave == (p0 & (NW - 1)) && !(LDSC && p0 == LC)) FIGH_WY_RETIRE(rn);
             }
 
             // ---- phase p: apply panel p to the trailing chunks; the owner of chunk p + 1 updates that chunk first and
@@ -787,7 +680,6 @@ __global__ __launch_bounds__(64 * NW, WPE) void tsqr_wy_kernel(const double *__r
                     const bool from_lds = LDSC && pn == LC;
                     if (from_lds) wy_update_lds_chunk<NRC>(lch, Vl, Tl, block(p, pn), lane, c, g);
                     else wy_update_chunk<NRC>(F.t, Vl, Tl, rp, block(p, pn), lane, c, g);
-                    FIGH_PROF_ADD(3);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) Rl[lane + 64 * r] = rq[r];
                     double *Vn = vt[vbn];
@@ -802,10 +694,8 @@ __global__ __launch_bounds__(64 * NW, WPE) void tsqr_wy_kernel(const double *__r
                         }
                     }
                     FIGH_WY_WAVE_SYNC();
-                    FIGH_PROF_ADD(7);
-                    wy_factor_panel<RPL>(X, Rl, red, Vn, Vn + M * kLdv, lane, c, g, null2);
+                    wy_factor_panel<RPL>(X, Rl, Vn, Vn + M * kLdv, lane, c, g, null2);
                     FIGH_WY_WAVE_SYNC();
-                    FIGH_PROF_ADD(4);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) bpp[lane + 64 * r] = Rl[lane + 64 * r];
                     // the queue rotation + the requests for the next tile's chunk (0.4-0.9 k cycles): with few slots per
@@ -861,14 +751,9 @@ __global__ __launch_bounds__(64 * NW, WPE) void tsqr_wy_kernel(const double *__r
                     }
                 }
                 if (owe) deferred = false;
-                FIGH_PROF_ADD(5);
                 __syncthreads();
-                FIGH_PROF_ADD(6);
                 if constexpr (kLateRetire) {
-                    if (is_owner && !(LDSC && pn == LC)) {
-                        FIGH_WY_RETIRE(rn);
-                        FIGH_PROF_ADD(11);
-                    }
+                    if (is_owner && !(LDSC && pn == LC)) FIGH_WY_RETIRE(rn);
                 }
                 vbp = vb;
                 vb = vbn;
@@ -881,7 +766,6 @@ __global__ __launch_bounds__(64 * NW, WPE) void tsqr_wy_kernel(const double *__r
 #undef FIGH_WY_LOAD
 #undef FIGH_WY_WAVE_SYNC
 #undef FIGH_WY_RETIRE
-    FIGH_PROF_STORE(prof, wave, NW);
 
     // ---- write this wave's columns of the nc x nc row-major triangle (zeros below the diagonal)
     double *Ro = Rout + (long)bx * nc * nc;
@@ -924,13 +808,6 @@ struct WyConfig {
 // independent panel chains per CU -- as the register file allows for the workgroup's tile.
 [[maybe_unused]] WyConfig wy_config(const int nc) {
     const int nch = (nc + 15) >> 4;
-#ifdef FIGH_ABLATION
-    if (const char *e = getenv("FIGH_WY_CFG")) {  // "nw,cpw,nrc,wpe" (ablation build only)
-        WyConfig cfg{0, 0, 0, 0, 0};  // a fifth number 1 selects the LDS-chunk form (one chunk beyond the register slots)
-        const int got = sscanf(e, "%d,%d,%d,%d,%d", &cfg.nw, &cfg.cpw, &cfg.nrc, &cfg.wpe, &cfg.ldsc);
-        if (got >= 4 && cfg.nw * cfg.cpw + (cfg.ldsc ? 1 : 0) >= nch) return cfg;
-    }
-#endif
     // the tallest tile the 256 registers of a wave hold: the rows one look-ahead chain covers are what the throughput is
     // proportional to (same-box A/B, n = 191: 64 -> 80 -> 96 rows +11 %, +5.5 %; n = 241: 64 -> 80 rows +6 %; the last
     // step of each costs 8 / 22 spilled registers and still wins)
@@ -970,23 +847,6 @@ bool wy_dispatch(const WyConfig cfg, F &&f) {
     FIGH_WY_CASE(4, 6, 3, 2)
     FIGH_WY_CASE_L(4, 6, 3, 2, true)
     FIGH_WY_CASE(8, 4, 4, 2)
-#ifdef FIGH_ABLATION
-    FIGH_WY_CASE(8, 3, 4, 2)
-    FIGH_WY_CASE(4, 3, 4, 2)
-    FIGH_WY_CASE(4, 3, 5, 2)
-    FIGH_WY_CASE(4, 4, 4, 2)
-    FIGH_WY_CASE(4, 3, 4, 3)
-    FIGH_WY_CASE(4, 4, 3, 3)
-    FIGH_WY_CASE(4, 3, 3, 3)
-    FIGH_WY_CASE(4, 4, 3, 2)
-    FIGH_WY_CASE(8, 2, 4, 3)
-    FIGH_WY_CASE(8, 2, 4, 2)
-    FIGH_WY_CASE(4, 3, 4, 1)
-    FIGH_WY_CASE(4, 6, 4, 1)
-    FIGH_WY_CASE(8, 3, 2, 4)
-    FIGH_WY_CASE(8, 3, 2, 3)
-    FIGH_WY_CASE(8, 4, 2, 3)
-#endif
 #undef FIGH_WY_CASE
 #undef FIGH_WY_CASE_L
     return false;

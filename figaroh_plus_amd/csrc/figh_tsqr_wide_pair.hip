@@ -53,7 +53,7 @@ int launch_tsqr_wide_pairs(const double *stack, long count, int nc, double *Rws_
                                            decltype(WPE)::value, decltype(LDSC)::value, 1>),
                            dim3((unsigned)nwg), dim3(64 * decltype(NW)::value), 0, stream(), stack, (long)nc, (long)nc,
                            (const int *)nullptr, nc, (const double *)nullptr, (const double *)nullptr, 1L, Rblk, Rws_out,
-                           nc, (long long *)nullptr, count, 0, null_pivot_sq());
+                           nc, count, 0, null_pivot_sq());
     };
     // More pairs than CUs (the stacked triangles of a streamed run: 20 chunks x 512 for the human model): the level is
     // throughput-bound, and the level-0 geometry -- four waves, two workgroups = two chains per CU -- absorbs twice as
@@ -179,7 +179,7 @@ int reduce_wide_stacks(std::vector<WyPairStack> &st) {
             hipLaunchKernelGGL((tsqr_wy_kernel<8, 2, 8, 2, false, 4>), dim3((unsigned)L.nwg), dim3(512), 0, stream(),
                                reinterpret_cast<const double *>(d_table + L.table_at), 0L, 0L, (const int *)nullptr, 0,
                                (const double *)nullptr, (const double *)nullptr, 1L, (double *)nullptr, (double *)nullptr, 0,
-                               (long long *)nullptr, 0L, (int)L.grouped.size(), null_pivot_sq());
+                               0L, (int)L.grouped.size(), null_pivot_sq());
             FIGH_HIP(hipGetLastError());
         }
     }
@@ -196,7 +196,7 @@ int launch_tsqr_wide_single(const double *W, long rows, long ldw, const int *col
         hipLaunchKernelGGL((tsqr_wy_kernel<decltype(NW)::value, decltype(CPW)::value, decltype(NRC)::value,
                                            decltype(WPE)::value, decltype(LDSC)::value, 0>),
                            dim3(1), dim3(64 * decltype(NW)::value), 0, stream(), W, rows, ldw, col_idx, n,
-                           (const double *)nullptr, (const double *)nullptr, 1L, Rblk, R_out, nc, (long long *)nullptr, 0L, 0,
+                           (const double *)nullptr, (const double *)nullptr, 1L, Rblk, R_out, nc, 0L, 0,
                            null_pivot_sq());
     });
     if (!ok) {

@@ -130,7 +130,7 @@ class IdentificationPipeline:
         # placement_trials > 1: when W is allocated, that many candidate buffers are allocated side by side, the regressor
         # kernel is timed on each and the fastest one is kept (set-up cost: a few passes of K1).  The time K1 needs for the
         # same 4 GB depends on the physical pages behind them -- 0.68 or 0.82 ms per allocation, hipMemset moves with it
-        # (0.60 / 0.63 ms), measured with tools/k1_alloc_probe.py -- and the allocator offers no handle on that.
+        # (0.60 / 0.63 ms), measured with an allocation probe since removed -- and the allocator offers no handle on that.
         self.placement_trials = max(1, int(placement_trials))
         self.placement_report = None
         self.robot, self.param, self.coupling = robot, param, coupling

@@ -59,6 +59,22 @@ def test_no_torch_or_oracle_in_product():
     assert "torch" not in out and "oracle" not in out
 
 
+def test_library_sources_have_no_runtime_switches():
+    """The shipped library has no run-time switches (bench.py relies on it) and no second, ablation build: no getenv
+    and no FIGH_ABLATION anywhere in its sources.  An experiment's knob is a compile-time #ifdef of its own branch."""
+    csrc = os.path.join(ROOT, "figaroh_plus_amd", "csrc")
+    found = []
+    for fn in sorted(os.listdir(csrc)):
+        path = os.path.join(csrc, fn)
+        if not os.path.isfile(path) or not (fn == "Makefile" or fn.endswith((".hip", ".h", ".cpp"))):
+            continue
+        with open(path) as f:
+            for no, line in enumerate(f, 1):
+                if "getenv" in line or "FIGH_ABLATION" in line:
+                    found.append("%s:%d: %s" % (fn, no, line.strip()))
+    assert not found, "run-time switches or ablation code in the library sources:\n" + "\n".join(found)
+
+
 def test_compute_fails_loudly_without_gpu(lib):
     if lib.device_count() > 0:
         pytest.skip("GPU present")

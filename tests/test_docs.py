@@ -40,3 +40,25 @@ def test_profiles_gputest_summaries_name_only_tests_that_exist():
         with open(path) as f:
             for name in set(re.findall(r"\b(test_[a-z0-9_]+)\b", f.read())):
                 assert name in defined or name in MODULES, (path, name)
+
+
+def test_tools_readme_names_only_files_that_exist():
+    """tools/README.md names only scripts that exist (a third of the tools referenced builds, switches or
+    scripts that were gone): the backticked file names in the first column of its table, and every tools/ path in the
+    text.  No glob patterns: each name is one file."""
+    with open(os.path.join(ROOT, "tools", "README.md")) as f:
+        text = f.read()
+    names = set()
+    for line in text.splitlines():
+        if not line.startswith("| `"):
+            continue
+        for span in re.findall(r"`([^`]+)`", line.split(" | ")[0]):
+            word = span.split()[0]
+            if re.search(r"\.(py|sh|hip)$|/$", word):
+                names.add(os.path.join("tools", word))
+    names.update(re.findall(r"\b(tools/[\w./*?-]*\w/?)", text))
+    assert len(names) > 40
+    globbed = sorted(n for n in names if any(ch in n for ch in "*?["))
+    assert not globbed, "glob patterns in tools/README.md: %s" % globbed
+    missing = sorted(n for n in names if not os.path.exists(os.path.join(ROOT, n)))
+    assert not missing, "tools/README.md names files that do not exist: %s" % missing

@@ -5,9 +5,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
 from figaroh_plus_amd import _lib
-if os.environ.get("FIGH_OLD_ABI"):  # a round-1 build: symbols added since are not there
-    for k in ("figh_regressor_build_padded", "figh_comm_available", "figh_place_block", "figh_host_wait_mode"):
-        _lib.SIGNATURES.pop(k, None)
 from figaroh_plus_amd.pipeline import IdentificationPipeline
 from figaroh_plus_amd.tools.robot import Robot
 meta = json.load(open(os.path.join(ROOT, "tests", "golden", "cfg2_ur10.json")))

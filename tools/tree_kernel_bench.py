@@ -1,5 +1,5 @@
 """K1' alone (figh_regressor_build on a tree model): kernel time by HIP events and algorithmic GB/s.
-usage: python tools/tree_kernel_bench.py [scale]   (FIGH_LIB_PATH / FIGH_TREE_TAPE select ablation variants)"""
+usage: python tools/tree_kernel_bench.py [scale]   (FIGH_LIB_PATH selects another build of the library)"""
 import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -33,7 +33,6 @@ for cfg, mn, N in (("cfg3_tiago", "tiago", 1_000_000), ("cfg4_talos", "talos", 4
     cnt, ms = _lib.profile_get("regressor_tree"); _lib.profile_enable(False)
     ms /= max(cnt, 1)
     byt = N * (8 * (robot.model.nq + 2 * robot.model.nv) + 8 * rps * ncols)
-    print("%-11s N=%d  K1' %.2f ms  %.0f GB/s algorithmic (%.1f%% of 8 TB/s)  layout=%s tape=%s" % (
-        cfg, N, ms, byt / ms / 1e6, 100 * byt / ms / 1e6 / 8000, "link-padded" if padded else "dense (reference)",
-        os.environ.get("FIGH_TREE_TAPE")), flush=True)
+    print("%-11s N=%d  K1' %.2f ms  %.0f GB/s algorithmic (%.1f%% of 8 TB/s)  layout=%s" % (
+        cfg, N, ms, byt / ms / 1e6, 100 * byt / ms / 1e6 / 8000, "link-padded" if padded else "dense (reference)"), flush=True)
     del W, d_q, d_v, d_a

@@ -10,7 +10,7 @@ from figaroh_plus_amd import _lib
 rows = int(float(sys.argv[1])) if len(sys.argv) > 1 else 1_000_000
 ns = [int(x) for x in sys.argv[2:]] or [191, 241, 331, 400]
 rng = np.random.default_rng(3)
-print("device", _lib.device_info()["name"], "lib", os.path.basename(_lib.LIB_PATH), "cfg", os.environ.get("FIGH_WY_CFG"), flush=True)
+print("device", _lib.device_info()["name"], "lib", os.path.basename(_lib.LIB_PATH), flush=True)
 for n in ns:
     t0 = time.perf_counter()
     small = rng.standard_normal((20000, n))
