@@ -125,7 +125,15 @@ def null_rule_bounds(R1, R2):
     return A_base, A_dep, float(np.abs(X).sum(axis=1).max())  # (the last: the infinity norm of R1^-1, for the bound on phi)
 
 
-def null_rule_certified(absdiag, idx_base, idx_regroup, bounds, tol_qr, safety=2.0, phi=None):
+def null_rule_triangles(rows, pieces=1):
+    """Upper bound of the number T of level-0 triangles a factorisation of ``rows`` rows makes, split into ``pieces``
+    separately launched parts (ranks x row blocks x sample chunks): every triangle absorbs at least one full tile of 48 or
+    64 rows except the ragged last one of a piece, so T <= rows / 32 + pieces.  (The kernels' own count follows the launch
+    geometry -- 512 .. 2048 per launch -- and is not reported through the ABI; this bound does not depend on it.)"""
+    return max(1, -(-int(rows) // 32) + max(1, int(pieces)))
+
+
+def null_rule_certified(absdiag, idx_base, idx_regroup, bounds, tol_qr, safety=2.0, phi=None, rows=None, pieces=1):
     """A-posteriori GUARD for a factorisation that ran WITH the null-pivot rule (``figh_tsqr_null_pivot_tol``): True when the
     classification ``|R_kk| > tol_qr`` can be trusted to be the one plain Householder -- the reference's ``np.linalg.qr``,
     qrdecomposition.py:205-221 -- gives on the same matrix; not certified = the caller repeats the factorisation WITHOUT the
@@ -151,6 +159,13 @@ def null_rule_certified(absdiag, idx_base, idx_regroup, bounds, tol_qr, safety=2
       error is ``cond eps``; the rule's is ``cond tol_qr / (64 |W_b|)``, some 1e4 times that, harmless for the BASELINE robots
       (cond(W_b) 1e2 .. 1e4) and not for an ill-conditioned base regressor (found by tools/fuzz_trees.py: two layouts of one
       random model, one under the rule and one not, residuals 1e-5 apart);
+    * with ``rows`` (the rows of the factored matrix): every base pivot further above ``tol_qr`` than ``safety (1 + A_k) sqrt(T)
+      tol_qr / 64``, T = :func:`null_rule_triangles` (``pieces``: see there).  A genuine base column whose residual is just below ``tol_qr / 64`` in
+      almost every level-0 triangle and sits in a few rows only is folded in all the others: up to ``sqrt(T) tol_qr / 64`` of
+      it, not ``tol_qr / 64``, keeps its direction in the columns behind it, and an exactly dependent column of it (coefficient
+      3, 4e6 rows, pivot 4.5e-8) shows a spurious pivot above ``tol_qr`` that the per-triangle margin lets through
+      (tests/test_qr_graded.py, the adversarial family).  A spurious base column has at most that much of a pivot, so the
+      margin catches it; the BASELINE robots' smallest base pivots (4e3 .. 6e3 at their full sizes) are far above it;
     * finite numbers throughout.
 
     For the five BASELINE robots A <= 9 and UR10, TALOS and the human model are certified at their full sizes; TIAGo, whose
@@ -172,4 +187,5 @@ def null_rule_certified(absdiag, idx_base, idx_regroup, bounds, tol_qr, safety=2
         return False
     if dd.size and dd.max() > tol_qr / 8.0:
         return False
-    return bool(np.all(db - tol_qr > (1.0 + A_base) * fold) and np.all(tol_qr - dd > (1.0 + A_dep) * fold))
+    fold_base = fold * (np.sqrt(null_rule_triangles(rows, pieces)) if rows is not None else 1.0)
+    return bool(np.all(db - tol_qr > (1.0 + A_base) * fold_base) and np.all(tol_qr - dd > (1.0 + A_dep) * fold))

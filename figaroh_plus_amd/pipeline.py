@@ -911,6 +911,13 @@ class IdentificationPipeline:
         _lib.check(lib.figh_memcpy_d2h(host.ctypes.data, pack.ptr, host.nbytes))
         return self._finish(host.reshape(nc + 1, nc), n, nc, params_r, idx_e, col_norm, with_tau, total_rows, strings)
 
+    def _level0_pieces(self, total_rows):
+        """Upper bound of the separately launched parts of a pass (ranks x row blocks x sample chunks), for the count of
+        level-0 triangles in the null-rule certificate (_host.null_rule_triangles)."""
+        N = max(1, int(self.N))
+        chunks = -(-N // int(self.chunk_samples)) if self.chunk_samples else 1
+        return max(1, int(total_rows) // N) * chunks
+
     def _finish(self, rows_k, n, nc, params_r, idx_e, col_norm, with_tau, total_rows, strings, defer_beta=False):
         """Host tail on the n x n numbers the device returns (qrdecomposition.py:215-266): ``rows_k`` ((nc + 1) x nc) holds,
         in the original column order, the rows of the regrouped factorisation qr([W1 W2 tau]) at the base columns and, in
@@ -965,7 +972,8 @@ class IdentificationPipeline:
         if self.null_pivots:
             from ._host import null_rule_certified
             d_, ib_, ir_, bounds_ = self._cert_args
-            out["null_rule_certified"] = null_rule_certified(d_, ib_, ir_, bounds_, self.tol_qr, phi=phi_ls if with_tau else None)
+            out["null_rule_certified"] = null_rule_certified(d_, ib_, ir_, bounds_, self.tol_qr, phi=phi_ls if with_tau else None,
+                                                             rows=total_rows, pieces=self._level0_pieces(total_rows))
         if strings and beta is not None:
             out["params_base"] = qrd._expressions([params_r[i] for i in idx_base],
                                                   [params_r[i] for i in idx_regroup], beta)

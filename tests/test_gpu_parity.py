@@ -310,6 +310,8 @@ def test_full_size_structural_invariants(lib, cfg, N, oracle_lib):
         assert out["params_base"] == g.meta["params_base"]
         # noise-free tau = W phi_ref: the identified base parameters are the regrouped standard ones
         assert np.abs(out["phi_ls"] - g["phi_from_std"]).max() <= 1e-6 * np.abs(g["phi_from_std"]).max()
+        # the null-pivot rule stays certified at the BASELINE size (sqrt(T) margin of _host.null_rule_certified)
+        assert out["null_rule_certified"] and pipe.null_rule_fallbacks == 0
     else:
         # TX40 at the script's 50 000 samples: one structurally dependent pivot is a genuine tiny number that
         # grows like sqrt(N) (2.5e-9 at N=400, 2.7e-8 here) and crosses TOL_QR=1e-8, so the REFERENCE's own
@@ -493,6 +495,7 @@ def test_full_size_talos(lib, oracle_lib):
     assert np.abs(out["phi_ls"] - g["phi_from_std"]).max() <= 1e-6 * np.abs(g["phi_from_std"]).max()
     dep = np.setdiff1d(np.arange(len(out["params_r"])), out["idx_base"])
     assert out["absdiagR"][dep].max() < 1e-8 < out["absdiagR"][out["idx_base"]].min()
+    assert out["null_rule_certified"] and pipe.null_rule_fallbacks == 0
     _spot_rows_padded(pipe, g, oracle_lib, qva, 6, rng)
 
 
@@ -507,6 +510,7 @@ def test_full_size_human_resident_link_compact(lib, oracle_lib):
     assert pipe._link_pos is not None and pipe.W.cols == 16 * 19
     assert out["idx_e"] == list(g["idx_e"]) and out["rows"] == 60_000_000
     assert out["idx_base"] == list(g["idx_base"]) and out["params_base"] == g.meta["params_base"]
+    assert out["null_rule_certified"] and pipe.null_rule_fallbacks == 0
     assert np.abs(out["phi_ls"] - g["phi_from_std"]).max() <= 1e-6 * np.abs(g["phi_from_std"]).max()
     _spot_rows_padded(pipe, g, oracle_lib, qva, 6, rng)
 
@@ -608,6 +612,7 @@ def test_full_size_human_streamed(lib):
     out = pipe.run()
     assert out["idx_e"] == list(g["idx_e"]) and out["rows"] == 60_000_000
     assert out["idx_base"] == list(g["idx_base"]) and out["params_base"] == g.meta["params_base"]
+    assert out["null_rule_certified"] and pipe.null_rule_fallbacks == 0
     assert np.abs(out["phi_ls"] - g["phi_from_std"]).max() <= 1e-6 * np.abs(g["phi_from_std"]).max()
 
 
@@ -1834,6 +1839,9 @@ def test_merge_tree_against_lapack(lib, nc, count):
     assert np.array_equal(R, np.triu(R))
     ref = np.linalg.qr(stack.reshape(-1, nc), mode="r")
     assert np.abs(np.abs(R) - np.abs(ref)).max() <= 1e-12 * np.abs(ref).max()
+    # ... and column by column: the 1e-3-scaled column is held to its own size, not to 1e-9 of it
+    cn = np.linalg.norm(stack.reshape(-1, nc), axis=0)
+    assert (np.abs(np.abs(R) - np.abs(ref)).max(axis=0) <= 1e-12 * cn).all()
     # bit-reproducible
     lib.tsqr_merge(d_stack, count, nc, d_R)
     assert np.array_equal(d_R.to_host().reshape(nc, nc), R)

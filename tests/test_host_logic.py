@@ -389,3 +389,84 @@ def test_bench_spawns_rank_processes_and_relays_their_failure():
         # one line, rank 0's (it quotes n_gpus for the headline and again for strong_scaling)
         lines = [json.loads(line) for line in out.splitlines() if line.startswith("{")]
         assert p.returncode == 0 and len(lines) == 1 and lines[0]["n_gpus"] == 2, out[-2000:]
+
+
+def test_null_rule_certificate_sqrt_triangles():
+    """With the rows of the factorisation, a base pivot must clear tol_qr by 2 (1 + A) sqrt(T) tol_qr / 64: a genuine base
+    column folded in almost every level-0 triangle leaks up to sqrt(T) tol_qr / 64 into the columns behind it (the
+    adversarial family of test_qr_graded.py: 4e6 rows, a spurious pivot above tol_qr).  Large pivots stay certified."""
+    from figaroh_plus_amd._host import null_rule_bounds, null_rule_certified, null_rule_triangles
+    tol = 1e-8
+    R1 = np.array([[1.0, 2.0, -3.0], [0.0, 4.5e-8, 4e-3], [0.0, 0.0, 5.0]])
+    bounds = null_rule_bounds(R1, np.c_[R1 @ np.ones(3), np.zeros(3)])
+    diag = np.array([1.0, 4.5e-8, 5.0, 1e-12, 0.0])
+    assert null_rule_triangles(4000000) == 125001 and null_rule_triangles(1) == 2 and null_rule_triangles(64, 24) == 26
+    assert null_rule_certified(diag, [0, 1, 2], [3, 4], bounds, tol)  # the per-triangle margin alone lets it through
+    assert null_rule_certified(diag, [0, 1, 2], [3, 4], bounds, tol, rows=64)
+    assert not null_rule_certified(diag, [0, 1, 2], [3, 4], bounds, tol, rows=4000000)
+    big = np.array([1.0, 4e3, 5.0, 1e-12, 0.0])  # UR10 / TALOS / human: smallest base pivots 4e3 .. 6e3 at full size
+    R1b = R1.copy()
+    R1b[1, 1] = 4e3
+    assert null_rule_certified(big, [0, 1, 2], [3, 4], null_rule_bounds(R1b, np.c_[R1b @ np.ones(3), np.zeros(3)]), tol,
+                               rows=6 * 10 ** 7)
+
+
+def test_graded_qr_exact_gram_against_python_integers():
+    """tests/qr_graded_common.exact_gram: the Gram of an integer matrix with power-of-two column scales and row block
+    weights equals Python-integer (exact rational) arithmetic."""
+    from fractions import Fraction
+
+    import qr_graded_common as qg
+    rng = np.random.default_rng(3)
+    M = qg.int_matrix(rng, 37, 6)
+    s = np.array([-30, 7, 0, -10, 30, 3])
+    e = np.repeat([-1, 0, 1], [10, 20, 7])
+    G = qg.exact_gram(M, s, e)
+    for i in range(6):
+        for j in range(6):
+            want = sum(Fraction(int(M[r, i]) * int(M[r, j])) * Fraction(2) ** int(2 * e[r]) for r in range(37))
+            want *= Fraction(2) ** int(s[i] + s[j])
+            assert Fraction(G[i, j]) == want
+    with pytest.raises(AssertionError):
+        qg.exact_gram(M + 0.5, s)
+
+
+@pytest.mark.parametrize("n", [1, 7, 40])
+def test_graded_qr_longdouble_cholesky_against_mpmath(n):
+    """tests/qr_graded_common.cholesky_ld against a 50-digit mpmath Cholesky of the same exact Gram, column by column."""
+    mpmath = pytest.importorskip("mpmath")
+    import qr_graded_common as qg
+    rng = np.random.default_rng(n)
+    M = qg.int_matrix(rng, 3 * n + 5, n)
+    s = qg.graded_scales(rng, n, -30, 30, [0, n - 1])
+    G = qg.exact_gram(M, s)
+    R = qg.cholesky_ld(G)
+    mpmath.mp.dps = 50
+    Rm = mpmath.cholesky(mpmath.matrix([[mpmath.mpf(float(x)) for x in row] for row in G])).T
+    nrm = qg.col_norms(G)
+    cond = qg.equilibrated_cond(R)
+    for j in range(n):
+        col = [mpmath.mpf(a) / b for a, b in (R[i, j].as_integer_ratio() for i in range(n))]  # (exact: 64-bit mantissas)
+        err = mpmath.sqrt(sum((col[i] - Rm[i, j]) ** 2 for i in range(n)))
+        assert float(err) / nrm[j] <= 64 * cond * cond * 2.0 ** -64
+
+
+def test_graded_qr_columnwise_metric_rejects_what_the_normwise_check_accepts():
+    """A planted error: LAPACK's R with a 1e-9 relative error in a 2^-20-scaled column.  The suite's older norm-wise check
+    (|R^T R - G| <= 1e-12 max |G|) accepts it; the column-wise metrics of test_qr_graded.py reject it."""
+    import qr_graded_common as qg
+    rng = np.random.default_rng(20)
+    n, rows = 30, 400
+    M = qg.int_matrix(rng, rows, n)
+    s = np.zeros(n, dtype=np.int64)
+    s[11] = -20
+    G = qg.exact_gram(M, s)
+    R = np.linalg.qr(M * np.ldexp(1.0, s), mode="r")
+    R_ref = qg.cholesky_ld(G)
+    cond = qg.equilibrated_cond(R_ref)
+    assert qg.backward_err(R, G) <= 1e-13 and qg.forward_err(R, R_ref, G) <= 200 * cond * 2.0 ** -53  # clean: both pass
+    R[:, 11] *= 1.0 + 1e-9
+    assert qg.normwise_backward_err(R, G) <= 1e-12
+    assert qg.backward_err(R, G) > 1e-13
+    assert qg.forward_err(R, R_ref, G) > 200 * cond * 2.0 ** -53
+    assert qg.diag_err(R, R_ref, G) > 200 * cond * 2.0 ** -53

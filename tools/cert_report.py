@@ -5,7 +5,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
 from figaroh_plus_amd import _lib
-from figaroh_plus_amd._host import null_rule_certified
+from figaroh_plus_amd._host import null_rule_certified, null_rule_triangles
 from figaroh_plus_amd.pipeline import IdentificationPipeline
 from figaroh_plus_amd.tools.randomdata import sample_inputs
 from figaroh_plus_amd.tools.robot import Robot
@@ -32,9 +32,10 @@ for c in (sys.argv[1:] or ["cfg1", "cfg2", "cfg3", "cfg4", "cfg5"]):
     line = "%s N %d: n_base %d, fallbacks %d, rule now %s" % (c, N, len(b), pipe.null_rule_fallbacks, pipe.null_pivots)
     if cache is not None and cache[1] is not None:
         Ab, Ad, xn = cache[1]
-        mb = (d[b] - 1e-8) / ((1 + Ab) * 2e-8 / 64); md = (1e-8 - d[dep]) / ((1 + Ad) * 2e-8 / 64) if len(dep) else np.array([np.inf])
+        sqT = np.sqrt(null_rule_triangles(out["rows"], pipe._level0_pieces(out["rows"])))  # the guard's base margin (_host.null_rule_certified)
+        mb = (d[b] - 1e-8) / ((1 + Ab) * 2e-8 / 64 * sqT); md = (1e-8 - d[dep]) / ((1 + Ad) * 2e-8 / 64) if len(dep) else np.array([np.inf])
         phi = np.abs(out["phi_ls"])
-        line += "; A_base max %.2f, A_dep max %.2f; tightest margin / bound: base %.2f (pivot %.4g, A %.2f), dependent %.2f; phi bound |R1^-1|_inf tol/64 |phi|_1 = %.2e against 1e-7 |phi|_inf = %.2e" % (
+        line += "; A_base max %.2f, A_dep max %.2f; tightest margin / bound: base (sqrt(T) tol/64) %.2f (pivot %.4g, A %.2f), dependent %.2f; phi bound |R1^-1|_inf tol/64 |phi|_1 = %.2e against 1e-7 |phi|_inf = %.2e" % (
             Ab.max(), Ad.max() if len(Ad) else 0, mb.min(), d[b][mb.argmin()], Ab[mb.argmin()], md.min(), xn * 1e-8 / 64 * phi.sum(), 1e-7 * max(1.0, phi.max()))
     failed = getattr(pipe, "_cert_failed", None)
     if failed is not None and failed[0] is not None and failed[0][1] is not None:
