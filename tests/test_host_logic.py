@@ -470,3 +470,160 @@ def test_graded_qr_columnwise_metric_rejects_what_the_normwise_check_accepts():
     assert qg.backward_err(R, G) > 1e-13
     assert qg.forward_err(R, R_ref, G) > 200 * cond * 2.0 ** -53
     assert qg.diag_err(R, R_ref, G) > 200 * cond * 2.0 ** -53
+
+
+# ------------------------------------------------------------------ structured graded generators (test_qr_structured_graded.py)
+@pytest.mark.parametrize("extra,dead_links,deps", [(True, (), False), (True, (2,), True), (False, (1, 4), True)])
+def test_wrench_generator_structure_layouts_and_gram(extra, dead_links, deps):
+    """tests/qr_graded_common.Wrench: the Gram is exact, the force rows are zero on slots < 6, the dependencies are exact
+    (and keep that zero pattern), and every device layout reads back to the reference-layout W."""
+    import qr_graded_common as qg
+    rng = np.random.default_rng([7, len(dead_links), int(deps)])
+    g = qg.Wrench(rng, 37, 6, 40 if extra else 36, -30, 30, dead_links=dead_links, extra_slots=extra, deps=deps)
+    W = g.reference()
+    assert not W[:3 * g.Nb][:, (np.arange(g.ncols) % 14) < 6].any()
+    assert np.count_nonzero(np.any(W != 0, axis=0)) == g.n and g.n <= 0.8 * g.ncols
+    if not extra:
+        assert not W[:, (np.arange(g.ncols) % 14) >= 10].any()
+    G = g.gram()
+    A = np.c_[W[:, g.kept], g.tau()]
+    assert np.array_equal(G, np.asarray(np.asarray(A, dtype=np.longdouble).T @ np.asarray(A, dtype=np.longdouble),
+                                        dtype=np.float64))
+    for k in g.dep:  # an inertia column stays zero in the force rows
+        assert g.slot[k] >= 6 or not W[:3 * g.Nb, g.kept[k]].any()
+    if deps:
+        assert len(g.dep) > 5
+        Gb = qg.cholesky_ld(g.gram(False)[np.ix_(g.base, g.base)])
+        assert float(np.diag(Gb).min()) > 0
+        R = np.linalg.qr(g.A(), mode="r")
+        assert (np.abs(np.diag(R))[g.dep] < 1e-6 * np.abs(np.diag(R)).max()).all()
+    # the layouts as figh.h states them, entry by entry (independent of the column maps the writers and readers share)
+    Wp, Wc = g.padded(), g.padded(compact=True)
+    for c in range(g.ncols):
+        l, s = divmod(c, 14)
+        assert np.array_equal(Wp[:, 16 * l + s], W[:, c])
+        if g.link_pos[l] >= 0:
+            assert np.array_equal(Wc[:, 16 * int(g.link_pos[l]) + s], W[:, c])
+        else:
+            assert not W[:, c].any()
+        if not extra:
+            for compact in (False, True):
+                buf, ldw = g.force_compact(compact)
+                ldf, half = g.force_ld(compact), 3 * g.Nb
+                F, T = buf[:half * ldf].reshape(half, ldf), buf[half * ldf:].reshape(half, ldw)
+                p = int(g.link_pos[l]) if compact else l
+                if p >= 0:
+                    assert np.array_equal(T[:, 16 * p + s], W[half:, c])
+                if 6 <= s < 10 and p >= 0:
+                    assert np.array_equal(F[:, 16 * (p // 4) + 4 * (p % 4) + s - 6], W[:half, c])
+    assert np.array_equal(qg.read_wrench_layout(W, g.rows, g.ncols, g.ncols), W)
+    Wp = g.padded()
+    assert np.array_equal(qg.read_wrench_layout(Wp, g.rows, g.ncols, Wp.shape[1], 16), W)
+    Wc = g.padded(compact=True)
+    assert Wc.shape[1] == 16 * g.nlive
+    assert np.array_equal(qg.read_wrench_layout(Wc, g.rows, g.ncols, Wc.shape[1], 16, g.link_pos), W)
+    if not extra:
+        for compact in (False, True):
+            buf, ldw = g.force_compact(compact)
+            ldf = g.force_ld(compact)
+            assert buf.size == 3 * g.Nb * (ldf + ldw)
+            back = qg.read_wrench_layout(buf, g.rows, g.ncols, ldw, 16, g.link_pos if compact else None, ldf)
+            assert np.array_equal(back, W)
+
+
+def _blocks_generator(deps=True, with_inactive=True):
+    import qr_graded_common as qg
+    rng = np.random.default_rng(41)
+    groups = [(2, [0, 1, 2, 3]), (5, [1, 2]), (7, [2]), (4, [3]), (3, [1])]
+    return qg.RowBlocks(rng, 50, 6, groups, -20, 20, inactive=[5] if with_inactive else [], deps=deps,
+                        noise={0: "tiny", 1: "big", 2: "mid", 3: "tiny"}, k_block=1)
+
+
+def test_row_block_generator_lists_layouts_and_residual_identity():
+    """tests/qr_graded_common.RowBlocks: every block is zero outside its list, the lists are what the matrix says, the
+    dense and block-compact writers hold the same entries, the dependencies stay inside the blocks that list them, and
+    ||tau_b - W_b phi||^2 = ||e_b||^2 exactly."""
+    import qr_graded_common as qg
+    g = _blocks_generator()
+    assert g.counts.tolist()[5] == -1 and g.counts[4] == 0  # block 4: tau only; block 5: inactive
+    for b in g.active():
+        L = set(g.lists[b].tolist())
+        outside = [c for c in range(g.n) if c not in L]
+        assert not g.Mb(b)[:, outside].any()
+        assert all(np.any(g.Mb(b)[:, c] != 0) for c in L)
+    for b in g.active():  # the dependencies keep every column inside the blocks of its group
+        assert np.array_equal(g.lists[b], np.flatnonzero(g.support[b]))
+    R = np.linalg.qr(g.A()[:5 * g.rows_b], mode="r")
+    assert len(g.dep) > 3 and (np.abs(np.diag(R))[g.dep] < 1e-9 * np.abs(np.diag(R)).max()).all()
+    W = g.dense(16)
+    flat, off, lds, local = g.compact()
+    counts, cols, pos = g.block_columns(16)
+    at = 0
+    for b in range(g.nblocks):
+        if counts[b] <= 0:
+            continue
+        Wb = flat[off[b]:off[b] + g.rows_b * lds[b]].reshape(g.rows_b, lds[b])
+        c = slice(at, at + counts[b])
+        assert np.array_equal(Wb[:, local[c]], W[b * g.rows_b:(b + 1) * g.rows_b][:, cols[c]])
+        assert np.array_equal(pos[c], g.lists[b])
+        at += counts[b]
+    phi = g.phi()
+    for b in g.active():
+        sl = slice(b * g.rows_b, (b + 1) * g.rows_b)
+        r = g.tau()[sl] - g.A()[sl] @ phi
+        assert np.array_equal(r, g.e[sl])
+    sq = [float(g.e[b * g.rows_b:(b + 1) * g.rows_b] @ g.e[b * g.rows_b:(b + 1) * g.rows_b]) for b in g.active()]
+    assert max(sq) / min(sq) >= 2.0 ** 14  # (the GPU cases spread it over 2^30: 4096-row blocks)
+    G = g.gram()
+    for b in g.active():
+        Gb = g.block_gram(b)
+        L = np.r_[g.lists[b], g.n]
+        v = np.r_[phi, -1.0][L]
+        assert float(np.asarray(v, dtype=np.longdouble) @ np.asarray(Gb, dtype=np.longdouble) @ v) == sq[g.active().index(b)]
+    assert np.diag(G).min() > 0
+    assert np.array_equal(g.stack_offsets(), np.r_[0, np.cumsum([max(c + 1, 0) for c in g.counts])])  # (inactive: no rows)
+
+
+def test_structured_planted_errors_rejected_columnwise_and_per_block():
+    """Planted errors in a per-block triangle stack built with LAPACK: a 1e-9 relative error in the rows of a small-scale
+    block, and in a small block's r^2.  The suite's older checks (|S^T S - G| <= 1e-11 max |G| for the stack, 1e-9 max
+    sigma^2 for the variances) accept them; the per-block column-wise checks of test_qr_structured_graded.py reject them."""
+    import qr_graded_common as qg
+    g = _blocks_generator(deps=False, with_inactive=False)
+    bexp = np.zeros(g.nblocks, dtype=np.int64)
+    bexp[0] = -12  # block 0: rows at a small scale (exact: a power of two)
+    nc = g.n + 1
+    off = g.stack_offsets()
+    S = np.zeros((int(off[-1]), nc))
+    e2, Gb = [], {}
+    for b in g.active():
+        L = np.r_[g.lists[b], g.n]
+        sl = slice(b * g.rows_b, (b + 1) * g.rows_b)
+        Rb = np.linalg.qr(np.c_[g.A()[sl][:, g.lists[b]], g.tau()[sl]] * 2.0 ** bexp[b], mode="r")
+        S[off[b]:off[b + 1], L] = Rb
+        Gb[b] = g.block_gram(b) * 4.0 ** bexp[b]
+        e2.append(float(g.e[sl] @ g.e[sl]) * 4.0 ** bexp[b])
+    e2 = np.array(e2)
+    G = np.asarray(g.gram(block_exp=bexp), dtype=np.float64)
+    v = np.r_[g.phi(), -1.0]
+    r2 = np.array([float(((S[off[b]:off[b + 1]] @ v) ** 2).sum()) for b in g.active()])
+
+    from test_qr_structured_graded import C_R2, TOL_BACKWARD  # (the tolerances the GPU tests apply)
+
+    def per_block(S):  # the backward metric of the GPU test's stack check, block by block
+        return max(qg.backward_err(S[off[b]:off[b + 1]][:, np.r_[g.lists[b], g.n]], Gb[b]) for b in g.active())
+
+    def r2_ok(r2):  # the GPU test's per-block residual check
+        return all(qg.residual_ratio(r2[i], e2[i], np.r_[g.phi()[g.lists[b]], -1.0], Gb[b]) <= C_R2
+                   for i, b in enumerate(g.active()))
+
+    assert per_block(S) <= TOL_BACKWARD and r2_ok(r2)  # clean: both pass
+    Sp = S.copy()
+    Sp[off[0]:off[1]] *= 1.0 + 1e-9
+    assert np.abs(Sp.T @ Sp - G).max() <= 1e-11 * np.abs(G).max()
+    assert per_block(Sp) > TOL_BACKWARD
+    r2p = r2.copy()
+    small = int(np.argmin(e2))
+    r2p[small] *= 1.0 + 1e-9
+    assert np.abs(r2p - e2).max() <= 1e-9 * e2.max()
+    assert not r2_ok(r2p)

@@ -156,25 +156,9 @@ def test_merge_graded_columns(lib, nc, count, profile, record_property):
 
 
 def _make_dependent(rng, X, s, n, lo):
-    """Make every third column k < n (k % 3 == 2) of ``X`` (last axis = columns: a matrix or a stack of triangles) an exact
-    combination, with coefficients +-1 .. +-3, of up to three earlier base columns of scale <= 2^-8 within 2^4 of each
-    other; ``s`` (the column exponents) is updated in place.  The combination is exact in float64 and its rounding residue
-    stays far below tol_qr / 3 (u times a column norm below 10^5).  A combination of upper-triangular columns is upper
-    triangular.  Returns (dependent, base) column lists."""
-    dep = [k for k in range(2, n) if k % 3 == 2]
-    base = [k for k in range(X.shape[-1]) if k not in dep]
-    for k in dep:
-        cand = [i for i in base if i < k and s[i] <= -8]
-        if not cand:
-            s[0] = max(lo, -8)
-            cand = [0]
-        anchor = s[rng.choice(cand)]
-        src = [i for i in cand if anchor <= s[i] <= anchor + 4]
-        src = list(rng.choice(src, min(3, len(src)), replace=False))
-        c = rng.integers(1, 4, len(src)) * rng.choice([-1, 1], len(src))
-        X[..., k] = sum(int(ci) * X[..., i] * 2.0 ** int(s[i] - anchor) for ci, i in zip(c, src))
-        s[k] = anchor
-    return dep, base
+    """Every third column k < n an exact combination of earlier base columns (qr_graded_common.make_dependent, one class
+    for all columns).  Returns (dependent, base) column lists."""
+    return qg.make_dependent(rng, X, s, n, lo)
 
 
 @pytest.mark.parametrize("profile", sorted(PROFILES))
