@@ -38,8 +38,8 @@ static hipEvent_t acquire_event() {
     return e;
 }
 
-static void *g_ws[40] = {nullptr};
-static size_t g_ws_bytes[40] = {0};
+static void *g_ws[kWorkspaceSlots] = {nullptr};
+static size_t g_ws_bytes[kWorkspaceSlots] = {0};
 
 void set_error(const std::string &msg) { g_error = msg; }
 
@@ -75,7 +75,7 @@ int ensure_device() {
     return FIGH_OK;
 }
 
-void *workspace(size_t bytes, int slot) {
+void *workspace(size_t bytes, WorkspaceSlot slot) {
     if (bytes <= g_ws_bytes[slot]) return g_ws[slot];
     if (g_ws[slot]) {
         (void)hipStreamSynchronize(g_stream);

@@ -557,8 +557,8 @@ static int launch_fused(const figh_model_s *m, int flags, long N, const double *
                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set[NJ] = true;
     }
-    double *part = static_cast<double *>(workspace(sizeof(double) * grid * G::NPROD * G::NC, 0));
-    double *Rws = static_cast<double *>(workspace(sizeof(double) * (size_t)nc * nc * (grid * ncons + 1), 5));
+    double *part = static_cast<double *>(workspace(sizeof(double) * grid * G::NPROD * G::NC, kWsRegressorNorms));
+    double *Rws = static_cast<double *>(workspace(sizeof(double) * (size_t)nc * nc * (grid * ncons + 1), kWsLevel0TriOrWrench));
     if (!part || !Rws) return FIGH_ERR_ALLOC;
     const ChainParams<NJ> P = chain_params<NJ>(m);
     {

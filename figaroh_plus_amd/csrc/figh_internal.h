@@ -73,8 +73,53 @@ LaunchEvents take_launch_events();  // the pair of the innermost at_launch scope
         hipExtLaunchKernelGGL(kernel, grid, block, lds, figh::stream(), ev_.start, ev_.stop, 0, __VA_ARGS__);    \
     } while (0)
 
+// The slots of the library's device scratch buffers.  A slot holds one buffer at a time: the users a name lists share it and
+// must never need it at the same time; buffers that are live together (one of them on the side stream included) have slots
+// of their own.
+enum WorkspaceSlot {
+    kWsRegressorNorms,      // per-workgroup diag(W^T W) partials: chain and tree regressor kernels, fused chain TSQR
+    kWsColsqParts,          // figh_colsq's per-block partials
+    kWsMergeA,              // merge-level outputs, ping: tsqr_reduce, launch_tsqr_tree, figh_regressor_tsqr_batch
+    kWsMergeB,              // ... pong
+    kWsBlockWeights,        // tsqr_level0: the row-block weights
+    kWsLevel0TriOrWrench,   // level-0 triangles: tsqr_level0 without a caller buffer, figh_fused.hip, the wrench torque stack
+    kWsHintFirst,           // tile_hint: the first columns of the hint blocks
+    kWsChunkW,              // W of a streamed chunk (figh_regressor_colsq, regressor_tsqr_impl) or of the whole batch
+    kWsChunkNormsOrCols,    // figh_regressor_colsq's chunk norms; the padded column list of the streamed and batched TSQR
+    kWsChunkTau,            // regressor_tsqr_impl: tau of a chunk
+    kWsChunkStack,          // level-0 triangles of all chunks (regressor_tsqr_impl) or trajectories (batch)
+    kWsGramR,               // figh_regressor_gram: R
+    kWsWideBlkOrFilter,     // Rblk of every blocked-kernel launcher (reduce_wide_stacks' too); the filtfilt work array
+    kWsTileHint,            // tile_hint: the per-tile hint (cached from call to call)
+    kWsZeroHint,            // zero_tile_hint
+    kWsOneTri,              // the plain triangle ahead of the rank decision: tsqr_reduce_stack, figh_tsqr_selected_blocks
+    kWsRevealPerm,          // reveal_triangle: the base permutation
+    kWsRevealR,             // reveal_triangle: the regrouped triangle
+    kWsSelectedHint,        // figh_tsqr_selected: the per-tile hint its selection kernel writes
+    kWsBatchPair,           // figh_regressor_tsqr_batch: the pair / interleaved stack that folds in d_R_stack
+    kWsChunkNormsFused,     // regressor_tsqr_impl: diag(W^T W) of a chunk
+    kWsForceCols,           // the force rows' column list: figh_tsqr_selected_wrench, regressor_tsqr_impl
+    kWsForceOrBlockTri,     // level-0 triangles: the wrench entry's force rows, the blocks entry's plain blocks
+    kWsForceOrBlockR,       // the force rows' triangle (wrench entry, regressor_tsqr_impl); the blocks entry's block triangles
+    kWsChunkForceStack,     // regressor_tsqr_impl: the force rows' level-0 triangles of all chunks
+    kWsBlockStack,          // figh_tsqr_selected_blocks: the compact stack when the caller keeps none
+    kWsCompactCounts,       // figh_compact_rows: kept rows per group
+    kWsCompactTotal,        // figh_compact_rows: kept rows in all
+    kWsGroupTri,            // launch_tsqr_group: the triangles of every level
+    kWsGroupJobs,           // launch_tsqr_group: the job table and maps
+    kWsGroupZeros,          // launch_tsqr_group: the zero tile hint
+    kWsStacksA,             // reduce_wide_stacks (side stream): level outputs, ping
+    kWsStacksB,             // ... pong
+    kWsStacksBlk,           // reduce_wide_stacks: Rblk of its grouped launches
+    kWsStacksJobs,          // reduce_wide_stacks: the job table
+    kWsBlocksWideTri,       // figh_tsqr_selected_blocks: level-0 triangles of the wide blocks
+    kWsLinkPos,             // regressor_tsqr_impl: the link map of the link-compact layout
+    kWsBlocksMidTri,        // figh_tsqr_selected_blocks: level-0 triangles of the mid blocks
+    kWorkspaceSlots
+};
+
 // scratch buffer owned by the library, grown on demand (device)
-void *workspace(size_t bytes, int slot);
+void *workspace(size_t bytes, WorkspaceSlot slot);
 
 // A second, high-priority stream for LATENCY-BOUND chains of small launches (the merge levels of a TSQR: a handful of
 // workgroups per launch, 45 .. 500 us per level whatever the number of pairs) that do not depend on the throughput-bound
@@ -91,19 +136,21 @@ struct SideStream {
 };
 void stream_wait(hipEvent_t ev);
 
-}  // namespace figh
-
-// internal (not part of include/figh.h, not exported by libfigh.so: hidden visibility): level 0 of the TSQR only, see
-// figh_linalg.hip
-#define FIGH_INTERNAL extern "C" __attribute__((visibility("hidden")))
-FIGH_INTERNAL int figh_tsqr_level0(const double *d_W, int64_t rows, int64_t ldw, const int32_t *d_col_idx, int n,
-                                   const double *d_tau, const double *h_block_weight, int nblocks, double *d_tri_out,
-                                   int64_t capacity, int64_t *count_out, double **ws_out);
-FIGH_INTERNAL int64_t figh_tsqr_level0_capacity(int nc);
-FIGH_INTERNAL int figh_tsqr_hint_begin(const int32_t *h_first_col, int nfirst, int64_t rows, int n, int nc);
-FIGH_INTERNAL void figh_tsqr_hint_end(void);
-
-namespace figh {
+// figh_linalg.hip: level 0 of the TSQR only.  hint: per-tile structure hint of the register-tile kernel (tile_hint, nullptr:
+// none); chain_wgs > 0: the blocked kernel (more than 80 columns) runs with exactly that many workgroups and chain_flags
+// (launch_tsqr_wide)
+struct Level0Options {
+    const int *hint = nullptr;
+    long chain_wgs = 0;
+    int chain_flags = 0;
+};
+int tsqr_level0(const double *d_W, int64_t rows, int64_t ldw, const int32_t *d_col_idx, int n, const double *d_tau,
+                const double *h_block_weight, int nblocks, double *d_tri_out, int64_t capacity, int64_t *count_out,
+                double **ws_out, const Level0Options &opt = {});
+int64_t tsqr_level0_capacity(int nc);
+// the device per-tile hint of row blocks that are zero in front of column h_first_col[b] (nullptr in *out for more than 80
+// columns: only the register-tile kernel reads it)
+int tile_hint(const int32_t *h_first_col, int nfirst, int64_t rows, int n, int nc, const int **out);
 
 // figh_regressor_tree.hip: K1' for kinematic trees (tape-driven); *colsq_done = 1 when diag(W^T W) was fused
 int launch_regressor_tree(const figh_model_s *m, int mode, int flags, int ft_mask, long N, const double *q,
@@ -120,9 +167,6 @@ long tree_force_ld(const figh_model_s *m, int mode, int flags, int ft_mask);
 long tsqr_wide_workgroups(int nc, int cus);
 int launch_tsqr_wide(const double *W, long rows, long ldw, const int *col_idx, int n, const double *tau,
                      const double *d_blkw, long rows_per_blk, int nc, long nwg, double *Rws_out, int chain_flags = 0);
-// figh_linalg.hip: the NEXT figh_tsqr_level0 call (more than 80 columns) runs with exactly `wgs` workgroups and these chain
-// flags (launch_tsqr_wide); consumed by that call
-void tsqr_level0_chain(long wgs, int chain_flags);
 // figh_linalg.hip, external wrench on a free-flyer root (figh_tsqr_selected_wrench): the kept columns that can be non-zero
 // in force rows (d_fsel: n columns, then n positions in the kept list) and the force rows' triangle over all kept columns
 int split_force_columns(const int *d_kept, int n, int link_stride, int *d_fsel, int force_compact = 0);

@@ -421,17 +421,6 @@ static size_t tsqr2_lds_bytes(int ncc, int nc, bool rlast = false) {
     return sizeof(double) * ((rlast ? 80 : 64) + 256 * (size_t)(lch * lch - (lch * (lch - 1)) / 2) - skip);
 }
 
-// per-tile structure hint of the register-tile kernel: g_tile_hint is installed by figh_tsqr_hint_begin for the level-0
-// launch of the NEXT figh_tsqr_level0 call only (the merge levels run on stacked triangles and never see it)
-static const int *g_tile_hint = nullptr;
-// chained level-0 launches of a streamed run (blocked kernel only): workgroup count and chain flags of the next call
-static long g_chain_wgs = 0;
-static int g_chain_flags = 0;
-void tsqr_level0_chain(long wgs, int chain_flags) {
-    g_chain_wgs = wgs;
-    g_chain_flags = chain_flags;
-}
-
 __global__ __launch_bounds__(256) void tile_hint_kernel(const int *__restrict__ first, const long hint_rows,
                                                         const long rows, const long ntiles, int *__restrict__ out) {
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
@@ -445,7 +434,7 @@ __global__ __launch_bounds__(256) void tile_hint_kernel(const int *__restrict__ 
 static const int *zero_tile_hint(long ntiles) {  // "no structure known": first possible non-zero = column 0 everywhere
     static size_t zeroed = 0;
     const size_t need = sizeof(int) * (size_t)(ntiles + 1);
-    int *z = static_cast<int *>(workspace(need, 15));
+    int *z = static_cast<int *>(workspace(need, kWsZeroHint));
     if (z && zeroed < need) {  // (re)allocated: workspace() hands out at least `need` bytes, growing by 25 %
         if (hipMemsetAsync(z, 0, need, stream()) != hipSuccess) return nullptr;
         zeroed = need;
@@ -516,7 +505,7 @@ static int tsqr_reduce(const double *Rs, long count, int nc, double *d_R_out) {
     }
     const double *cur = Rs;
     long cnt = count;
-    int slot = 2;
+    WorkspaceSlot slot = kWsMergeA;
     while (cnt > 1) {
         ProfileScope scope("tsqr_reduce");
         long nb;
@@ -545,9 +534,16 @@ static int tsqr_reduce(const double *Rs, long count, int nc, double *d_R_out) {
         }
         cur = dst;
         cnt = nb;
-        slot = slot == 2 ? 3 : 2;
+        slot = slot == kWsMergeA ? kWsMergeB : kWsMergeA;
     }
     if (cur != d_R_out) FIGH_HIP(hipMemcpyAsync(d_R_out, cur, tri, hipMemcpyDeviceToDevice, stream()));
+    return FIGH_OK;
+}
+
+// `count` triangles -> one in d_R_out (a lone triangle is copied)
+static int reduce_to_one(const double *tri, long count, int nc, double *d_R_out) {
+    if (count > 1) return tsqr_reduce(tri, count, nc, d_R_out);
+    FIGH_HIP(hipMemcpyAsync(d_R_out, tri, sizeof(double) * (size_t)nc * nc, hipMemcpyDeviceToDevice, stream()));
     return FIGH_OK;
 }
 
@@ -569,7 +565,7 @@ int figh_colsq(const double *d_W, int64_t rows, int cols, int64_t ldw, double *d
     long rpb = (rows + nblocks - 1) / nblocks;
     if (rpb < 16) rpb = 16;
     nblocks = (rows + rpb - 1) / rpb;
-    double *part = static_cast<double *>(workspace(sizeof(double) * nblocks * cols, 1));
+    double *part = static_cast<double *>(workspace(sizeof(double) * nblocks * cols, kWsColsqParts));
     if (!part) return FIGH_ERR_ALLOC;
     ProfileScope scope("colsq");
     hipLaunchKernelGGL(colsq_kernel, dim3((unsigned)nblocks), dim3(256), 0, stream(), d_W, (long)rows, cols, (long)ldw,
@@ -620,8 +616,8 @@ int figh_compact_rows(const double *d_W, int64_t rows, int cols, int64_t ldw, co
     *h_count_out = 0;
     if (rows == 0) return FIGH_OK;
     const long ngroups = (rows + 63) / 64;
-    int *cnt = static_cast<int *>(workspace(sizeof(int) * (size_t)ngroups + 16, 27));
-    long *total = static_cast<long *>(workspace(sizeof(long), 28));
+    int *cnt = static_cast<int *>(workspace(sizeof(int) * (size_t)ngroups + 16, kWsCompactCounts));
+    long *total = static_cast<long *>(workspace(sizeof(long), kWsCompactTotal));
     if (!cnt || !total) return FIGH_ERR_ALLOC;
     ProfileScope scope("compact_rows");
     const unsigned grid = (unsigned)((rows + 255) / 256);
@@ -674,17 +670,15 @@ int figh_block_sqnorm(const double *d_a, const double *d_b, int64_t rows, int nb
     return FIGH_OK;
 }
 
-// Level 0 only (internal, figh_internal.h): the per-wave / per-workgroup triangles of W go to d_tri_out (compact
-// nc x nc each, at most `capacity` of them, *count_out written) -- or, with d_tri_out == nullptr, to the library
-// workspace whose address is returned in *ws_out.  The streamed entry points stack the triangles of all their sample
-// chunks this way and run the merge tree once.
-int figh_tsqr_level0(const double *d_W, int64_t rows, int64_t ldw, const int32_t *d_col_idx, int n, const double *d_tau,
-                     const double *h_block_weight, int nblocks, double *d_tri_out, int64_t capacity, int64_t *count_out,
-                     double **ws_out) {
-    const long chain_wgs = g_chain_wgs;  // (consumed by this call whatever its outcome)
-    const int chain_flags = g_chain_flags;
-    g_chain_wgs = 0;
-    g_chain_flags = 0;
+}  // extern "C"
+
+// Level 0 only (figh_internal.h): the per-wave / per-workgroup triangles of W go to d_tri_out (compact nc x nc each, at
+// most `capacity` of them, *count_out written) -- or, with d_tri_out == nullptr, to the library workspace whose address
+// is returned in *ws_out.  The streamed entry points stack the triangles of all their sample chunks this way and run the
+// merge tree once.
+int figh::tsqr_level0(const double *d_W, int64_t rows, int64_t ldw, const int32_t *d_col_idx, int n, const double *d_tau,
+                      const double *h_block_weight, int nblocks, double *d_tri_out, int64_t capacity, int64_t *count_out,
+                      double **ws_out, const Level0Options &opt) {
     FIGH_REQUIRE(d_W && count_out, "NULL device pointer");
     FIGH_REQUIRE(rows > 0 && n > 0 && ldw > 0, "bad shape");
     const int nc = n + (d_tau ? 1 : 0);
@@ -698,7 +692,7 @@ int figh_tsqr_level0(const double *d_W, int64_t rows, int64_t ldw, const int32_t
     long rows_per_blk = 1;
     if (h_block_weight) {
         FIGH_REQUIRE(nblocks > 0 && rows % nblocks == 0, "rows must be a multiple of nblocks");
-        double *wbuf = static_cast<double *>(workspace(sizeof(double) * nblocks, 4));
+        double *wbuf = static_cast<double *>(workspace(sizeof(double) * nblocks, kWsBlockWeights));
         if (!wbuf) return FIGH_ERR_ALLOC;
         FIGH_HIP(hipMemcpyAsync(wbuf, h_block_weight, sizeof(double) * nblocks, hipMemcpyHostToDevice, stream()));
         FIGH_HIP(hipStreamSynchronize(stream()));
@@ -713,7 +707,7 @@ int figh_tsqr_level0(const double *d_W, int64_t rows, int64_t ldw, const int32_t
         // -- when there are rows for eight waves per CU (same-box A/B in alternating order, a probe since removed: 3e6 x 77:
         // 2.10-2.21 against 2.30-2.45 ms, 1e6 x 66: 0.74 against 0.85-0.92 ms, 1e6 x 80: equal; 5e5 x 80: 0.59-0.61 against
         // 0.53-0.75)
-        const bool small_lds = nc > 64 && !g_tile_hint && rows >= 6L * nc * cu_count() * 8;
+        const bool small_lds = nc > 64 && !opt.hint && rows >= 6L * nc * cu_count() * 8;
         long per_cu = (long)((160 * 1024) / tsqr2_lds_bytes(nc <= 64 ? 4 : 5, nc, small_lds));
         if (per_cu > ((nc <= 64 || small_lds) ? 8 : 4)) per_cu = (nc <= 64 || small_lds) ? 8 : 4;
         if (per_cu < 1) per_cu = 1;
@@ -726,21 +720,19 @@ int figh_tsqr_level0(const double *d_W, int64_t rows, int64_t ldw, const int32_t
         if (cap < 1) cap = 1;
         if (target > cap) target = cap;
     }
-    const long nw_est = (nc > 80 && chain_wgs > target ? chain_wgs : target) + 1;
+    const long nw_est = (nc > 80 && opt.chain_wgs > target ? opt.chain_wgs : target) + 1;
     double *Rws = d_tri_out;
     if (Rws) {
         FIGH_REQUIRE(capacity >= nw_est, "figh_tsqr_level0: triangle buffer too small");
     } else {
-        Rws = static_cast<double *>(workspace(sizeof(double) * (size_t)nc * nc * nw_est, 5));
+        Rws = static_cast<double *>(workspace(sizeof(double) * (size_t)nc * nc * nw_est, kWsLevel0TriOrWrench));
         if (!Rws) return FIGH_ERR_ALLOC;
     }
-    const int *hint = g_tile_hint;  // consumed by this launch only
-    g_tile_hint = nullptr;
     long nw = 0;
     {
         ProfileScope scope(rows >= 65536 ? "tsqr" : "tsqr_small", true);
-        if (int rc = tsqr_level(d_W, rows, ldw, d_col_idx, n, d_tau, d_blkw, rows_per_blk, nc, target, Rws, &nw, hint,
-                                chain_wgs, chain_flags))
+        if (int rc = tsqr_level(d_W, rows, ldw, d_col_idx, n, d_tau, d_blkw, rows_per_blk, nc, target, Rws, &nw, opt.hint,
+                                opt.chain_wgs, opt.chain_flags))
             return rc;
     }
     *count_out = nw;
@@ -748,45 +740,29 @@ int figh_tsqr_level0(const double *d_W, int64_t rows, int64_t ldw, const int32_t
     return FIGH_OK;
 }
 
-// upper bound of the triangles one figh_tsqr_level0 call can produce (for sizing the stack of a streamed run)
-int64_t figh_tsqr_level0_capacity(int nc) {
+// upper bound of the triangles one tsqr_level0 call can produce (for sizing the stack of a streamed run)
+int64_t figh::tsqr_level0_capacity(int nc) {
     if (nc > 80) return (int64_t)tsqr_wide_workgroups(nc, cu_count()) + 1;
     return (int64_t)cu_count() * 8 + 1;
 }
 
-int figh_tsqr(const double *d_W, int64_t rows, int64_t ldw, const int32_t *d_col_idx, int n, const double *d_tau,
-              const double *h_block_weight, int nblocks, double *d_R_out) {
-    FIGH_REQUIRE(d_W && d_R_out, "NULL device pointer");
-    int64_t nw = 0;
-    double *Rws = nullptr;
-    if (int rc = figh_tsqr_level0(d_W, rows, ldw, d_col_idx, n, d_tau, h_block_weight, nblocks, nullptr, 0, &nw, &Rws))
-        return rc;
-    const int nc = n + (d_tau ? 1 : 0);
-    if (nw == 1) {
-        FIGH_HIP(hipMemcpyAsync(d_R_out, Rws, sizeof(double) * (size_t)nc * nc, hipMemcpyDeviceToDevice, stream()));
-        return FIGH_OK;
-    }
-    return tsqr_reduce(Rws, nw, nc, d_R_out);
-}
-
-
-// internal (figh_internal.h): install / remove the structure hint for the next level-0 launches on `rows` rows
-int figh_tsqr_hint_begin(const int32_t *h_first_col, int nfirst, int64_t rows, int n, int nc) {
+// the structure hint for level-0 launches on `rows` rows (figh_internal.h)
+int figh::tile_hint(const int32_t *h_first_col, int nfirst, int64_t rows, int n, int nc, const int **out) {
     FIGH_REQUIRE(h_first_col && nfirst > 0 && rows > 0 && rows % nfirst == 0, "rows must be a multiple of the hint blocks");
     for (int b = 0; b < nfirst; ++b) FIGH_REQUIRE(h_first_col[b] >= 0 && h_first_col[b] <= n, "first column out of range");
     if (int rc = ensure_device()) return rc;
-    g_tile_hint = nullptr;
+    *out = nullptr;
     if (nc > 80) return FIGH_OK;  // only the register-tile kernel uses the hint
     // the per-tile form of the hint is cached: the pipeline passes the same structure every step
     static std::vector<int32_t> cached_first;
     static int64_t cached_rows = -1;
     static const int *cached_ptr = nullptr;
     const long ntiles = (rows + 63) / 64;
-    int *d_tile = static_cast<int *>(workspace(sizeof(int) * (size_t)(ntiles + 1), 14));
+    int *d_tile = static_cast<int *>(workspace(sizeof(int) * (size_t)(ntiles + 1), kWsTileHint));
     if (!d_tile) return FIGH_ERR_ALLOC;
     if (cached_ptr != d_tile || cached_rows != rows || cached_first.size() != (size_t)nfirst ||
         !std::equal(cached_first.begin(), cached_first.end(), h_first_col)) {
-        int *d_first = static_cast<int *>(workspace(sizeof(int) * nfirst, 7));
+        int *d_first = static_cast<int *>(workspace(sizeof(int) * nfirst, kWsHintFirst));
         if (!d_first) return FIGH_ERR_ALLOC;
         FIGH_HIP(hipMemcpyAsync(d_first, h_first_col, sizeof(int) * nfirst, hipMemcpyHostToDevice, stream()));
         hipLaunchKernelGGL(tile_hint_kernel, dim3((unsigned)((ntiles + 255) / 256)), dim3(256), 0, stream(), d_first,
@@ -797,49 +773,46 @@ int figh_tsqr_hint_begin(const int32_t *h_first_col, int nfirst, int64_t rows, i
         cached_rows = rows;
         cached_ptr = d_tile;
     }
-    g_tile_hint = d_tile;
+    *out = d_tile;
     return FIGH_OK;
 }
-void figh_tsqr_hint_end(void) { g_tile_hint = nullptr; }
 
-int figh_tsqr_structured(const double *d_W, int64_t rows, int64_t ldw, const int32_t *d_col_idx, int n,
-                         const double *d_tau, const double *h_block_weight, int nblocks, const int32_t *h_first_col,
-                         int nfirst, double *d_R_out) {
-    if (int rc = figh_tsqr_hint_begin(h_first_col, nfirst, rows, n, n + (d_tau ? 1 : 0))) return rc;
-    const int rc = figh_tsqr(d_W, rows, ldw, d_col_idx, n, d_tau, h_block_weight, nblocks, d_R_out);
-    figh_tsqr_hint_end();
-    return rc;
+// figh_tsqr with an optional structure hint: level 0, then its triangles -> one
+static int tsqr_hinted(const double *d_W, int64_t rows, int64_t ldw, const int32_t *d_col_idx, int n, const double *d_tau,
+                       const double *h_block_weight, int nblocks, const int *hint, double *d_R_out) {
+    FIGH_REQUIRE(d_W && d_R_out, "NULL device pointer");
+    int64_t nw = 0;
+    double *Rws = nullptr;
+    if (int rc = tsqr_level0(d_W, rows, ldw, d_col_idx, n, d_tau, h_block_weight, nblocks, nullptr, 0, &nw, &Rws, {hint}))
+        return rc;
+    return reduce_to_one(Rws, nw, n + (d_tau ? 1 : 0), d_R_out);
 }
 
-int figh_tsqr_merge(const double *d_Rs, int count, int nc, double *d_R_out) {
-    FIGH_REQUIRE(d_Rs && d_R_out, "NULL device pointer");
-    FIGH_REQUIRE(count >= 1 && nc >= 1 && nc <= 512, "bad shape");
-    if (int rc = ensure_device()) return rc;
-    if (count == 1) {
-        FIGH_HIP(hipMemcpyAsync(d_R_out, d_Rs, sizeof(double) * (size_t)nc * nc, hipMemcpyDeviceToDevice, stream()));
-        return FIGH_OK;
-    }
-    return tsqr_reduce(d_Rs, count, nc, d_R_out);
-}
-
-
-int figh_select_columns(const double *d_colsq, int ncols, double tol_e, int link_stride, int32_t *d_sel) {
-    FIGH_REQUIRE(d_colsq && d_sel, "NULL device pointer");
-    FIGH_REQUIRE(ncols >= 1 && ncols <= 1024, "figh_select_columns: 1 .. 1024 columns");
-    FIGH_REQUIRE(link_stride == 14 || link_stride == 16, "link_stride must be 14 (reference layout) or 16 (link-padded)");
-    if (int rc = ensure_device()) return rc;
+// select_columns_kernel under its profiling scope; with d_tile it also writes the per-tile hint (one workgroup per 256 tiles)
+static int select_columns(unsigned grid, const double *d_colsq, int ncols, double tol_e, int link_stride, int nblocks,
+                          long rows, long rows_per_block, long ntiles, int32_t *d_sel, int *d_tile, const int32_t *d_link_pos) {
     ProfileScope scope("select_columns");
-    hipLaunchKernelGGL(select_columns_kernel, dim3(1), dim3(256), 0, stream(), d_colsq, ncols, tol_e, link_stride, 0, 0L,
-                       1L, 0L, d_sel, (int *)nullptr, (const int *)nullptr);
+    hipLaunchKernelGGL(select_columns_kernel, dim3(grid), dim3(256), 0, stream(), d_colsq, ncols, tol_e, link_stride, nblocks,
+                       rows, rows_per_block, ntiles, d_sel, d_tile, (const int *)d_link_pos);
     FIGH_HIP(hipGetLastError());
     return FIGH_OK;
+}
+
+// the checks of the figh_tsqr_selected* entries after their pointers: the column count, the layout, the entry's shape and
+// row blocks (blocks_ok, blocks_msg), then the device
+static int check_selected(int ncols, int link_stride, bool shape_ok, bool blocks_ok, const char *blocks_msg) {
+    FIGH_REQUIRE(ncols >= 1 && ncols <= 1024, "figh_tsqr_selected: 1 .. 1024 columns");
+    FIGH_REQUIRE(link_stride == 14 || link_stride == 16, "link_stride must be 14 (reference layout) or 16 (link-padded)");
+    FIGH_REQUIRE(shape_ok, "bad shape");
+    FIGH_REQUIRE(blocks_ok, blocks_msg);
+    return ensure_device();
 }
 
 // plain triangle -> rows of the regrouped factorisation in the original column order + the plain diagonal (see figh.h)
 static int reveal_triangle(const double *d_R, int nc, int n_free, double tol_qr, double *d_rows_out) {
     if (nc <= 80) return merge_one_launch(d_R, 0, nc, n_free, tol_qr, nullptr, d_rows_out);
-    int *perm = static_cast<int *>(workspace(sizeof(int) * (size_t)nc, 17));
-    double *Rr = static_cast<double *>(workspace(sizeof(double) * (size_t)nc * nc, 18));
+    int *perm = static_cast<int *>(workspace(sizeof(int) * (size_t)nc, kWsRevealPerm));
+    double *Rr = static_cast<double *>(workspace(sizeof(double) * (size_t)nc * nc, kWsRevealR));
     if (!perm || !Rr) return FIGH_ERR_ALLOC;
     if (int rc = figh_base_permutation(d_R, nc, n_free, tol_qr, perm)) return rc;
     {
@@ -853,12 +826,10 @@ static int reveal_triangle(const double *d_R, int nc, int n_free, double tol_qr,
     return FIGH_OK;
 }
 
-}  // extern "C"
-
 // stack of `count` triangles -> one; tol_qr >= 0: + rank decision and regrouped rows ((nc+1) x nc), else the plain triangle
 int figh::tsqr_reduce_stack(const double *d_Rs, long count, int nc, int n_free, double tol_qr, double *d_out) {
     if (tol_qr < 0.0) return figh_tsqr_merge(d_Rs, (int)count, nc, d_out);
-    double *one = static_cast<double *>(workspace(sizeof(double) * (size_t)nc * nc, 16));
+    double *one = static_cast<double *>(workspace(sizeof(double) * (size_t)nc * nc, kWsOneTri));
     if (!one) return FIGH_ERR_ALLOC;
     if (count == 1) {
         if (nc <= 80) return reveal_triangle(d_Rs, nc, n_free, tol_qr, d_out);  // (one launch, touches no workspace)
@@ -874,52 +845,70 @@ int figh::tsqr_reduce_stack(const double *d_Rs, long count, int nc, int n_free, 
     return reveal_triangle(one, nc, n_free, tol_qr, d_out);
 }
 
-extern "C" {
-
-static int tsqr_selected_impl(const double *d_W, int64_t rows, int64_t ldw, const double *d_colsq, int ncols, double tol_e,
-                              int link_stride, int nblocks, int n_expected, const double *d_tau, double tol_qr, int32_t *d_sel,
-                              double *d_R_out, const int32_t *d_link_pos);
-int figh_tsqr_selected(const double *d_W, int64_t rows, int64_t ldw, const double *d_colsq, int ncols, double tol_e,
-                       int link_stride, int nblocks, int n_expected, const double *d_tau, double tol_qr, int32_t *d_sel,
-                       double *d_R_out) {
-    return tsqr_selected_impl(d_W, rows, ldw, d_colsq, ncols, tol_e, link_stride, nblocks, n_expected, d_tau, tol_qr, d_sel,
-                              d_R_out, nullptr);
-}
 static int tsqr_selected_impl(const double *d_W, int64_t rows, int64_t ldw, const double *d_colsq, int ncols, double tol_e,
                               int link_stride, int nblocks, int n_expected, const double *d_tau, double tol_qr, int32_t *d_sel,
                               double *d_R_out, const int32_t *d_link_pos) {
     FIGH_REQUIRE(d_W && d_colsq && d_sel, "NULL device pointer");
-    FIGH_REQUIRE(ncols >= 1 && ncols <= 1024, "figh_tsqr_selected: 1 .. 1024 columns");
-    FIGH_REQUIRE(link_stride == 14 || link_stride == 16, "link_stride must be 14 (reference layout) or 16 (link-padded)");
-    FIGH_REQUIRE(rows > 0 && n_expected <= ncols, "bad shape");
-    FIGH_REQUIRE(nblocks >= 0 && nblocks <= kMaxJoints && (nblocks == 0 || rows % nblocks == 0),
-                 "rows must be a multiple of the hint blocks");
-    if (int rc = ensure_device()) return rc;
+    if (int rc = check_selected(ncols, link_stride, rows > 0 && n_expected <= ncols,
+                                nblocks >= 0 && nblocks <= kMaxJoints && (nblocks == 0 || rows % nblocks == 0),
+                                "rows must be a multiple of the hint blocks"))
+        return rc;
     const int nc = n_expected + (d_tau ? 1 : 0);
     const bool hinted = nblocks > 0 && n_expected > 0 && nc <= 80 && rows / nblocks >= 1;
     const long ntiles = (rows + 63) / 64;
     int *d_tile = nullptr;
     if (hinted) {
-        d_tile = static_cast<int *>(workspace(sizeof(int) * (size_t)(ntiles + 1), 19));
+        d_tile = static_cast<int *>(workspace(sizeof(int) * (size_t)(ntiles + 1), kWsSelectedHint));
         if (!d_tile) return FIGH_ERR_ALLOC;
     }
-    {
-        ProfileScope scope("select_columns");
-        const long grid = hinted ? (ntiles + 255) / 256 : 1;
-        hipLaunchKernelGGL(select_columns_kernel, dim3((unsigned)grid), dim3(256), 0, stream(), d_colsq, ncols, tol_e,
-                           link_stride, hinted ? nblocks : 0, (long)rows, hinted ? (long)(rows / nblocks) : 1L,
-                           hinted ? ntiles : 0L, d_sel, d_tile, (const int *)d_link_pos);
-        FIGH_HIP(hipGetLastError());
-    }
+    if (int rc = select_columns(hinted ? (unsigned)((ntiles + 255) / 256) : 1u, d_colsq, ncols, tol_e, link_stride,
+                                hinted ? nblocks : 0, (long)rows, hinted ? (long)(rows / nblocks) : 1L, hinted ? ntiles : 0L,
+                                d_sel, d_tile, d_link_pos))
+        return rc;
     if (n_expected <= 0) return FIGH_OK;  // selection only (the caller does not know the count yet)
     FIGH_REQUIRE(d_R_out, "NULL device pointer");
-    g_tile_hint = d_tile;  // consumed by the level-0 launch below
     int64_t nw = 0;
     double *Rws = nullptr;
-    const int rc0 = figh_tsqr_level0(d_W, rows, ldw, d_sel + 2, n_expected, d_tau, nullptr, 0, nullptr, 0, &nw, &Rws);
-    g_tile_hint = nullptr;
-    if (rc0) return rc0;
+    if (int rc = tsqr_level0(d_W, rows, ldw, d_sel + 2, n_expected, d_tau, nullptr, 0, nullptr, 0, &nw, &Rws, {d_tile}))
+        return rc;
     return tsqr_reduce_stack(Rws, nw, nc, n_expected, tol_qr, d_R_out);
+}
+
+extern "C" {
+
+int figh_tsqr(const double *d_W, int64_t rows, int64_t ldw, const int32_t *d_col_idx, int n, const double *d_tau,
+              const double *h_block_weight, int nblocks, double *d_R_out) {
+    return tsqr_hinted(d_W, rows, ldw, d_col_idx, n, d_tau, h_block_weight, nblocks, nullptr, d_R_out);
+}
+
+int figh_tsqr_structured(const double *d_W, int64_t rows, int64_t ldw, const int32_t *d_col_idx, int n,
+                         const double *d_tau, const double *h_block_weight, int nblocks, const int32_t *h_first_col,
+                         int nfirst, double *d_R_out) {
+    const int *hint = nullptr;
+    if (int rc = tile_hint(h_first_col, nfirst, rows, n, n + (d_tau ? 1 : 0), &hint)) return rc;
+    return tsqr_hinted(d_W, rows, ldw, d_col_idx, n, d_tau, h_block_weight, nblocks, hint, d_R_out);
+}
+
+int figh_tsqr_merge(const double *d_Rs, int count, int nc, double *d_R_out) {
+    FIGH_REQUIRE(d_Rs && d_R_out, "NULL device pointer");
+    FIGH_REQUIRE(count >= 1 && nc >= 1 && nc <= 512, "bad shape");
+    if (int rc = ensure_device()) return rc;
+    return reduce_to_one(d_Rs, count, nc, d_R_out);
+}
+
+int figh_select_columns(const double *d_colsq, int ncols, double tol_e, int link_stride, int32_t *d_sel) {
+    FIGH_REQUIRE(d_colsq && d_sel, "NULL device pointer");
+    FIGH_REQUIRE(ncols >= 1 && ncols <= 1024, "figh_select_columns: 1 .. 1024 columns");
+    FIGH_REQUIRE(link_stride == 14 || link_stride == 16, "link_stride must be 14 (reference layout) or 16 (link-padded)");
+    if (int rc = ensure_device()) return rc;
+    return select_columns(1, d_colsq, ncols, tol_e, link_stride, 0, 0L, 1L, 0L, d_sel, nullptr, nullptr);
+}
+
+int figh_tsqr_selected(const double *d_W, int64_t rows, int64_t ldw, const double *d_colsq, int ncols, double tol_e,
+                       int link_stride, int nblocks, int n_expected, const double *d_tau, double tol_qr, int32_t *d_sel,
+                       double *d_R_out) {
+    return tsqr_selected_impl(d_W, rows, ldw, d_colsq, ncols, tol_e, link_stride, nblocks, n_expected, d_tau, tol_qr, d_sel,
+                              d_R_out, nullptr);
 }
 
 // figh_tsqr_selected for the external-wrench regressor of a free-flyer model (six row blocks of rows / 6 rows: three force
@@ -937,12 +926,9 @@ int figh_tsqr_selected_wrench(const double *d_W, int64_t rows, int64_t ldw, cons
     // no split: unknown counts, the register-tile kernel's column range (no chained form), nothing to gain, odd shapes
     if (n_expected <= 0 || nf_expected <= 0 || nf_expected >= n_expected || nc <= 80 || rows % 6 != 0 ||
         rows / 2 < 16L * nc) {
-        if (ld_force > 0) {
-            // (the plain pass reads every row over one column list: not what a force-compact W offers.  Selection only --
-            // the caller learns the counts and comes back with them -- or refuse)
-            if (n_expected <= 0)
-                return tsqr_selected_impl(d_W, rows, ldw, d_colsq, ncols, tol_e, link_stride, 0, n_expected, d_tau, tol_qr,
-                                          d_sel, d_R_out, d_link_pos);
+        // (the plain pass reads every row over one column list: not what a force-compact W offers.  Selection only -- the
+        // caller learns the counts and comes back with them -- or refuse)
+        if (ld_force > 0 && n_expected > 0) {
             set_error("force-compact W needs the force / torque split: more than 80 kept columns, some of them inertia columns, "
                       "at least 32 x columns rows");
             return FIGH_ERR_UNSUPPORTED;
@@ -951,31 +937,23 @@ int figh_tsqr_selected_wrench(const double *d_W, int64_t rows, int64_t ldw, cons
                                   d_R_out, d_link_pos);
     }
     FIGH_REQUIRE(d_W && d_colsq && d_sel && d_R_out, "NULL device pointer");
-    FIGH_REQUIRE(ncols >= 1 && ncols <= 1024, "figh_tsqr_selected: 1 .. 1024 columns");
-    FIGH_REQUIRE(link_stride == 14 || link_stride == 16, "link_stride must be 14 (reference layout) or 16 (link-padded)");
-    FIGH_REQUIRE(n_expected <= ncols, "bad shape");
-    if (int rc = ensure_device()) return rc;
-    {
-        ProfileScope scope("select_columns");
-        hipLaunchKernelGGL(select_columns_kernel, dim3(1), dim3(256), 0, stream(), d_colsq, ncols, tol_e, link_stride, 0,
-                           (long)rows, 1L, 0L, d_sel, (int *)nullptr, (const int *)d_link_pos);
-        FIGH_HIP(hipGetLastError());
-    }
+    if (int rc = check_selected(ncols, link_stride, n_expected <= ncols, true, nullptr)) return rc;
+    if (int rc = select_columns(1, d_colsq, ncols, tol_e, link_stride, 0, (long)rows, 1L, 0L, d_sel, nullptr, d_link_pos))
+        return rc;
     const int n = n_expected, nf = nf_expected, ncf = nf + (d_tau ? 1 : 0);
-    int *fsel = static_cast<int *>(workspace(sizeof(int) * 2 * (size_t)n, 22));
+    int *fsel = static_cast<int *>(workspace(sizeof(int) * 2 * (size_t)n, kWsForceCols));
     if (!fsel) return FIGH_ERR_ALLOC;
     if (int rc = split_force_columns(d_sel + 2, n, link_stride, fsel, ld_force > 0 ? 1 : 0)) return rc;  // (zero-fills behind the count)
     const int64_t rows_f = rows / 2;
     const int64_t ldf = ld_force > 0 ? ld_force : ldw;  // force-compact: the force rows are a matrix of their own
     // ---- force rows: their own TSQR over nf columns, reduced to one triangle
-    const int64_t cap_f = figh_tsqr_level0_capacity(ncf);
-    double *tri_f = static_cast<double *>(workspace(sizeof(double) * (size_t)ncf * ncf * cap_f, 23));
-    double *Rf = static_cast<double *>(workspace(sizeof(double) * (size_t)ncf * ncf, 24));
+    const int64_t cap_f = tsqr_level0_capacity(ncf);
+    double *tri_f = static_cast<double *>(workspace(sizeof(double) * (size_t)ncf * ncf * cap_f, kWsForceOrBlockTri));
+    double *Rf = static_cast<double *>(workspace(sizeof(double) * (size_t)ncf * ncf, kWsForceOrBlockR));
     if (!tri_f || !Rf) return FIGH_ERR_ALLOC;
     int64_t cnt_f = 0;
-    if (int rc = figh_tsqr_level0(d_W, rows_f, ldf, fsel, nf, d_tau, nullptr, 0, tri_f, cap_f, &cnt_f, nullptr)) return rc;
-    if (cnt_f == 1) FIGH_HIP(hipMemcpyAsync(Rf, tri_f, sizeof(double) * (size_t)ncf * ncf, hipMemcpyDeviceToDevice, stream()));
-    else if (int rc = tsqr_reduce(tri_f, cnt_f, ncf, Rf)) return rc;
+    if (int rc = tsqr_level0(d_W, rows_f, ldf, fsel, nf, d_tau, nullptr, 0, tri_f, cap_f, &cnt_f, nullptr)) return rc;
+    if (int rc = reduce_to_one(tri_f, cnt_f, ncf, Rf)) return rc;
     // ---- torque rows: chained launch, workgroup 0 starts from the embedded force triangle, the others from zeros
     long wgs = tsqr_wide_workgroups(nc, cu_count());
     {
@@ -987,12 +965,13 @@ int figh_tsqr_selected_wrench(const double *d_W, int64_t rows, int64_t ldw, cons
     // from it, no extra element -- was measured first: the CHAIN instantiation of the TALOS geometry carries 180 bytes of
     // scratch against the plain one's 68 and ran the torque rows in 105.6 ms)
     const size_t tri = sizeof(double) * (size_t)nc * nc;
-    double *stack = static_cast<double *>(workspace(tri * (size_t)(wgs + 3), 5));
+    double *stack = static_cast<double *>(workspace(tri * (size_t)(wgs + 3), kWsLevel0TriOrWrench));
     if (!stack) return FIGH_ERR_ALLOC;
     int64_t cnt = 0;
-    if (wgs > 64) tsqr_level0_chain(wgs - 1, 0);  // one workgroup less: with the embedded triangle the stack is 2^k again
-    if (int rc = figh_tsqr_level0(d_W + rows_f * ldf, rows - rows_f, ldw, d_sel + 2, n, d_tau ? d_tau + rows_f : nullptr,
-                                  nullptr, 0, stack, wgs + 2, &cnt, nullptr))
+    Level0Options torque;
+    if (wgs > 64) torque.chain_wgs = wgs - 1;  // one workgroup less: with the embedded triangle the stack is 2^k again
+    if (int rc = tsqr_level0(d_W + rows_f * ldf, rows - rows_f, ldw, d_sel + 2, n, d_tau ? d_tau + rows_f : nullptr, nullptr,
+                             0, stack, wgs + 2, &cnt, nullptr, torque))
         return rc;
     hipLaunchKernelGGL(embed_force_triangle_kernel, dim3(1), dim3(1024), 0, stream(), Rf, ncf, nf, fsel + n, nc, n,
                        stack + (size_t)cnt * nc * nc);
@@ -1014,17 +993,12 @@ int figh_tsqr_selected_blocks(const double *d_W, int64_t rows, int64_t ldw, cons
                               const double *d_tau, double tol_qr, int32_t *d_sel, double *d_R_out, double *d_block_tri) {
     FIGH_REQUIRE(d_W && d_colsq && d_sel && d_R_out && h_counts && d_cols && d_pos, "NULL pointer");
     FIGH_REQUIRE((h_block_off == nullptr) == (h_block_ld == nullptr), "block offsets and leading dimensions come together");
-    FIGH_REQUIRE(ncols >= 1 && ncols <= 1024, "figh_tsqr_selected: 1 .. 1024 columns");
-    FIGH_REQUIRE(link_stride == 14 || link_stride == 16, "link_stride must be 14 (reference layout) or 16 (link-padded)");
-    FIGH_REQUIRE(n_expected >= 1 && n_expected <= ncols && n_expected < 512, "bad shape");
-    FIGH_REQUIRE(nblocks >= 1 && nblocks <= kMaxJoints && rows % nblocks == 0, "rows must be a multiple of the row blocks");
-    if (int rc = ensure_device()) return rc;
-    {
-        ProfileScope scope("select_columns");
-        hipLaunchKernelGGL(select_columns_kernel, dim3(1), dim3(256), 0, stream(), d_colsq, ncols, tol_e, link_stride, 0,
-                           (long)rows, 1L, 0L, d_sel, (int *)nullptr, (const int *)nullptr);
-        FIGH_HIP(hipGetLastError());
-    }
+    if (int rc = check_selected(ncols, link_stride, n_expected >= 1 && n_expected <= ncols && n_expected < 512,
+                                nblocks >= 1 && nblocks <= kMaxJoints && rows % nblocks == 0,
+                                "rows must be a multiple of the row blocks"))
+        return rc;
+    if (int rc = select_columns(1, d_colsq, ncols, tol_e, link_stride, 0, (long)rows, 1L, 0L, d_sel, nullptr, nullptr))
+        return rc;
     const int n = n_expected, nc = n + (d_tau ? 1 : 0);
     const int64_t rows_b = rows / nblocks;
     int nmax = 1;
@@ -1043,12 +1017,12 @@ int figh_tsqr_selected_blocks(const double *d_W, int64_t rows, int64_t ldw, cons
     for (int j = 0; j < nblocks; ++j)
         if (h_counts[j] > 0 || (d_tau && h_counts[j] == 0)) rows_total += h_counts[j] + (d_tau ? 1 : 0);
     double *stack = d_block_tri ? d_block_tri
-                                : static_cast<double *>(workspace(sizeof(double) * (size_t)(rows_total + nc + 1) * nc, 26));
-    const int64_t cap_b = std::max(figh_tsqr_level0_capacity(nmax), figh_tsqr_level0_capacity(std::min(nmax, 80)));
-    double *tri_b = static_cast<double *>(workspace(sizeof(double) * (size_t)nmax * nmax * cap_b, 23));
+                                : static_cast<double *>(workspace(sizeof(double) * (size_t)(rows_total + nc + 1) * nc, kWsBlockStack));
+    const int64_t cap_b = std::max(tsqr_level0_capacity(nmax), tsqr_level0_capacity(std::min(nmax, 80)));
+    double *tri_b = static_cast<double *>(workspace(sizeof(double) * (size_t)nmax * nmax * cap_b, kWsForceOrBlockTri));
     // one triangle per row block (embedded at the end, in block order: an embedding zero-fills nc rows from its offset)
-    double *Rb_all = static_cast<double *>(workspace(sizeof(double) * (size_t)nmax * nmax * nblocks, 24));
-    double *one = static_cast<double *>(workspace(tri, 16));
+    double *Rb_all = static_cast<double *>(workspace(sizeof(double) * (size_t)nmax * nmax * nblocks, kWsForceOrBlockR));
+    double *one = static_cast<double *>(workspace(tri, kWsOneTri));
     if (!stack || !tri_b || !Rb_all || !one) return FIGH_ERR_ALLOC;
     // the WIDE blocks (more than 80 columns: the blocked kernel, one triangle per workgroup) keep their level-0 triangles
     // until all of them are there and are then reduced together, level by level (reduce_wide_stacks: one launch per level for
@@ -1056,9 +1030,9 @@ int figh_tsqr_selected_blocks(const double *d_W, int64_t rows, int64_t ldw, cons
     size_t wide_doubles = 0;
     for (int j = 0; j < nblocks; ++j) {
         const int ncj = h_counts[j] + (d_tau ? 1 : 0);
-        if (h_counts[j] > 0 && ncj > 80) wide_doubles += (size_t)ncj * ncj * (size_t)figh_tsqr_level0_capacity(ncj);
+        if (h_counts[j] > 0 && ncj > 80) wide_doubles += (size_t)ncj * ncj * (size_t)tsqr_level0_capacity(ncj);
     }
-    double *wide_tri = wide_doubles ? static_cast<double *>(workspace(sizeof(double) * wide_doubles, 36)) : nullptr;
+    double *wide_tri = wide_doubles ? static_cast<double *>(workspace(sizeof(double) * wide_doubles, kWsBlocksWideTri)) : nullptr;
     if (wide_doubles && !wide_tri) return FIGH_ERR_ALLOC;
     size_t wide_at = 0;
     std::vector<WyPairStack> wide;
@@ -1097,9 +1071,9 @@ int figh_tsqr_selected_blocks(const double *d_W, int64_t rows, int64_t ldw, cons
     size_t mid_doubles = 0, mid_at = 0;
     for (int j = 0; j < nblocks; ++j) {
         const int ncj = h_counts[j] + (d_tau ? 1 : 0);
-        if (h_counts[j] > 0 && ncj > 64 && ncj <= 80) mid_doubles += (size_t)ncj * ncj * (size_t)figh_tsqr_level0_capacity(ncj);
+        if (h_counts[j] > 0 && ncj > 64 && ncj <= 80) mid_doubles += (size_t)ncj * ncj * (size_t)tsqr_level0_capacity(ncj);
     }
-    double *mid_tri = mid_doubles ? static_cast<double *>(workspace(sizeof(double) * mid_doubles, 38)) : nullptr;
+    double *mid_tri = mid_doubles ? static_cast<double *>(workspace(sizeof(double) * mid_doubles, kWsBlocksMidTri)) : nullptr;
     if (mid_doubles && !mid_tri) return FIGH_ERR_ALLOC;
     // what every block is and where its rows of the stack / entries of the column lists start
     enum { SKIP, JOB, WIDE, MID, PLAIN };
@@ -1146,24 +1120,23 @@ int figh_tsqr_selected_blocks(const double *d_W, int64_t rows, int64_t ldw, cons
             int64_t cnt = 0;
             double *Rb = Rb_all + (size_t)j * nmax * nmax;
             if (kind[j] == WIDE || kind[j] == MID) {
-                const int64_t cap_j = figh_tsqr_level0_capacity(ncj);
+                const int64_t cap_j = tsqr_level0_capacity(ncj);
                 double *tri_j = kind[j] == WIDE ? wide_tri + wide_at : mid_tri + mid_at;
                 (kind[j] == WIDE ? wide_at : mid_at) += (size_t)ncj * ncj * (size_t)cap_j;
-                if (int rc = figh_tsqr_level0(Wj, rows_b, ldj, cols_j, nj, tj, nullptr, 0, tri_j, cap_j, &cnt, nullptr)) return rc;
+                if (int rc = tsqr_level0(Wj, rows_b, ldj, cols_j, nj, tj, nullptr, 0, tri_j, cap_j, &cnt, nullptr)) return rc;
                 if (kind[j] == WIDE) wide.push_back({tri_j, (long)cnt, ncj, Rb});
                 else mids.push_back({tri_j, (long)cnt, ncj, Rb});
                 embeds.push_back({j, Rb, ncj, nj, pos_j, out_j});
                 continue;
             }
             if (nj > 0) {
-                if (int rc = figh_tsqr_level0(Wj, rows_b, ldj, cols_j, nj, tj, nullptr, 0, tri_b, cap_b, &cnt, nullptr)) return rc;
+                if (int rc = tsqr_level0(Wj, rows_b, ldj, cols_j, nj, tj, nullptr, 0, tri_b, cap_b, &cnt, nullptr)) return rc;
             } else {
                 // (only tau in this block: its norm still counts) a 1 x 1 "matrix", the tau rows alone, through the same
                 // kernel with tau as its only column
-                if (int rc = figh_tsqr_level0(tj, rows_b, 1, nullptr, 1, nullptr, nullptr, 0, tri_b, cap_b, &cnt, nullptr)) return rc;
+                if (int rc = tsqr_level0(tj, rows_b, 1, nullptr, 1, nullptr, nullptr, 0, tri_b, cap_b, &cnt, nullptr)) return rc;
             }
-            if (cnt == 1) FIGH_HIP(hipMemcpyAsync(Rb, tri_b, sizeof(double) * (size_t)ncj * ncj, hipMemcpyDeviceToDevice, stream()));
-            else if (int rc = tsqr_reduce(tri_b, cnt, ncj, Rb)) return rc;
+            if (int rc = reduce_to_one(tri_b, cnt, ncj, Rb)) return rc;
             embeds.push_back({j, Rb, ncj, nj, pos_j, out_j});
         }
         if (phase == 0 && !wide.empty()) {
@@ -1176,12 +1149,8 @@ int figh_tsqr_selected_blocks(const double *d_W, int64_t rows, int64_t ldw, cons
     GroupEmbed group_embed;
     if (!jobs.empty())
         if (int rc = launch_tsqr_group(jobs, nc, n, cu_count(), &group_embed)) return rc;
-    for (const MidStack &ms : mids) {
-        if (ms.cnt == 1)
-            FIGH_HIP(hipMemcpyAsync(ms.R, ms.tri, sizeof(double) * (size_t)ms.ncj * ms.ncj, hipMemcpyDeviceToDevice, stream()));
-        else if (int rc = tsqr_reduce(ms.tri, ms.cnt, ms.ncj, ms.R))
-            return rc;
-    }
+    for (const MidStack &ms : mids)
+        if (int rc = reduce_to_one(ms.tri, ms.cnt, ms.ncj, ms.R)) return rc;
     stream_wait(wide_done);
     // (the embedding zero-fills nc rows from its offset and writes the block's ncj rows: the rows behind them belong to the next
     // block, whose own embedding follows in stream order; the buffer ends nc rows behind the last block)
@@ -1206,7 +1175,7 @@ int figh_tsqr_selected_blocks(const double *d_W, int64_t rows, int64_t ldw, cons
     }
     int64_t nw = 0;
     double *Rws = nullptr;
-    if (int rc = figh_tsqr_level0(stack, row_off, nc, nullptr, nc, nullptr, nullptr, 0, nullptr, 0, &nw, &Rws)) return rc;
+    if (int rc = tsqr_level0(stack, row_off, nc, nullptr, nc, nullptr, nullptr, 0, nullptr, 0, &nw, &Rws)) return rc;
     return tsqr_reduce_stack(Rws, nw, nc, n, tol_qr, d_R_out);
 }
 

@@ -373,7 +373,7 @@ static int launch_chain(const figh_model_s *m, int flags, long N, const double *
     const int vec_ok = (ldw % G::VEC == 0) && ((reinterpret_cast<uintptr_t>(W) % (8 * G::VEC)) == 0);
     ProfileScope scope("regressor_chain", true);
     if (d_colsq) {
-        double *part = static_cast<double *>(workspace(sizeof(double) * grid * G::NC, 0));
+        double *part = static_cast<double *>(workspace(sizeof(double) * grid * G::NC, kWsRegressorNorms));
         if (!part) return FIGH_ERR_ALLOC;
         FIGH_LAUNCH_TIMED((regressor_chain_kernel<NJ, TX40, true>), dim3((unsigned)grid), dim3(64), lds, P, flags, N, q, v, a,
                           W, ldw, vec_ok, part);

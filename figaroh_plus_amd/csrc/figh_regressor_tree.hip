@@ -1053,7 +1053,7 @@ int launch_regressor_tree(const figh_model_s *m, int mode, int flags, int ft_mas
     if (grid < 1) grid = 1;
     double *part = nullptr;
     if (fuse) {
-        part = static_cast<double *>(workspace(sizeof(double) * grid * ncols_int, 0));
+        part = static_cast<double *>(workspace(sizeof(double) * grid * ncols_int, kWsRegressorNorms));
         if (!part) return FIGH_ERR_ALLOC;
     }
     ProfileScope scope("regressor_tree", true);

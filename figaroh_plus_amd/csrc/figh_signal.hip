@@ -151,7 +151,7 @@ extern "C" int figh_filtfilt_cols(const double *d_X, int64_t rows, int cols, int
     const int64_t Lout = (L + q - 1) / q;
     if (rows_out) *rows_out = Lout * nblocks;
     const int64_t nseq = (int64_t)nblocks * cols;
-    double *work = static_cast<double *>(workspace(sizeof(double) * (size_t)(L + 2 * (int64_t)padlen) * nseq, 13));
+    double *work = static_cast<double *>(workspace(sizeof(double) * (size_t)(L + 2 * (int64_t)padlen) * nseq, kWsWideBlkOrFilter));
     if (!work) return FIGH_ERR_ALLOC;
     ProfileScope scope("filtfilt_cols");
     const dim3 grid((unsigned)((nseq + 63) / 64)), block(64);

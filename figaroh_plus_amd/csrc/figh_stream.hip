@@ -45,6 +45,14 @@ int64_t default_chunk(int rps, int ncols) {
     return c < 64 ? 64 : c;
 }
 
+// the caller's column list on the host (a NULL list = all n columns)
+int host_column_list(const int32_t *d_col_idx, int n, std::vector<int32_t> &cols) {
+    cols.resize(n);
+    if (d_col_idx) return figh_memcpy_d2h(cols.data(), d_col_idx, sizeof(int32_t) * n);
+    for (int c = 0; c < n; ++c) cols[c] = c;
+    return FIGH_OK;
+}
+
 }  // namespace
 
 extern "C" int figh_regressor_colsq(figh_model_t model, int mode, int flags, int ft_mask, int64_t N, const double *d_q,
@@ -65,8 +73,8 @@ extern "C" int figh_regressor_colsq(figh_model_t model, int mode, int flags, int
     }
     if (chunk_samples == 0) chunk_samples = default_chunk(rps, ncols);
     const int64_t cs = chunk_samples < N ? chunk_samples : N;
-    double *Wc = static_cast<double *>(workspace(sizeof(double) * (size_t)rps * cs * ncols, 8));
-    double *part = static_cast<double *>(workspace(sizeof(double) * ncols, 9));
+    double *Wc = static_cast<double *>(workspace(sizeof(double) * (size_t)rps * cs * ncols, kWsChunkW));
+    double *part = static_cast<double *>(workspace(sizeof(double) * ncols, kWsChunkNormsOrCols));
     if (!Wc || !part) return FIGH_ERR_ALLOC;
     const int nq = model->host.nq, nv = model->host.nv;
     for (int64_t lo = 0; lo < N; lo += cs) {
@@ -124,7 +132,7 @@ static int regressor_tsqr_impl(figh_model_t model, int mode, int flags, int ft_m
     const int64_t nchunks = (N + cs - 1) / cs;
     // diag(W^T W) of all columns fused into the regressor kernel of every chunk (the elimination's input, for a caller that
     // factors the columns it EXPECTS to be kept and verifies the set afterwards: no separate norms pass over the samples)
-    double *cs_part = d_colsq_out ? static_cast<double *>(workspace(sizeof(double) * ncols, 21)) : nullptr;
+    double *cs_part = d_colsq_out ? static_cast<double *>(workspace(sizeof(double) * ncols, kWsChunkNormsFused)) : nullptr;
     if (d_colsq_out && !cs_part) return FIGH_ERR_ALLOC;
     FIGH_REQUIRE(!(flags & FIGH_FLAG_BLOCKED_INPUTS) || nchunks == 1 || cs % 64 == 0,
                  "tile-blocked inputs: chunk_samples must be a multiple of 64");
@@ -140,49 +148,41 @@ static int regressor_tsqr_impl(figh_model_t model, int mode, int flags, int ft_m
     if (nlive > 0) {
         // a caller may list columns of links without entries (identically zero columns: the SIP program passes the inertial
         // columns of EVERY link, identification_tools.py:528-531): those exist in the link-padded layout only
-        std::vector<int32_t> cols(n);
-        if (d_col_idx) {
-            if (int rc = figh_memcpy_d2h(cols.data(), d_col_idx, sizeof(int32_t) * n)) return rc;
-        } else {
-            for (int c = 0; c < n; ++c) cols[c] = c;
-        }
+        std::vector<int32_t> cols;
+        if (int rc = host_column_list(d_col_idx, n, cols)) return rc;
         for (int c = 0; c < n && nlive > 0; ++c)
             if (cols[c] < 0 || cols[c] / 14 >= model->host.nlinks || link_pos[cols[c] / 14] < 0) nlive = -1;
     }
     if (nlive > 0) {
-        d_link_pos = static_cast<int *>(workspace(sizeof(int) * kMaxJoints, 37));
+        d_link_pos = static_cast<int *>(workspace(sizeof(int) * kMaxJoints, kWsLinkPos));
         if (!d_link_pos) return FIGH_ERR_ALLOC;
         FIGH_HIP(hipMemcpyAsync(d_link_pos, link_pos, sizeof(int) * model->host.nlinks, hipMemcpyHostToDevice, stream()));
         FIGH_HIP(hipStreamSynchronize(stream()));  // (link_pos lives on this stack frame)
         flags |= FIGH_FLAG_LINK_COMPACT;
     }
     const int64_t ldc = padded ? 16 * (int64_t)(nlive > 0 ? nlive : model->host.nlinks) : ncols;
-    double *Wc = static_cast<double *>(workspace(sizeof(double) * (size_t)rps * cs * ldc, 8));
+    double *Wc = static_cast<double *>(workspace(sizeof(double) * (size_t)rps * cs * ldc, kWsChunkW));
     int32_t *d_cols = const_cast<int32_t *>(d_col_idx);
     if (padded) {
-        d_cols = static_cast<int32_t *>(workspace(sizeof(int32_t) * (size_t)n, 9));
+        d_cols = static_cast<int32_t *>(workspace(sizeof(int32_t) * (size_t)n, kWsChunkNormsOrCols));
         if (!d_cols) return FIGH_ERR_ALLOC;
         hipLaunchKernelGGL(pad_columns_kernel, dim3((n + 255) / 256), dim3(256), 0, stream(), d_col_idx, n, d_cols,
                            (const int *)d_link_pos);
         FIGH_HIP(hipGetLastError());
     }
-    double *tc = d_tau ? static_cast<double *>(workspace(sizeof(double) * (size_t)rps * cs, 10)) : nullptr;
+    double *tc = d_tau ? static_cast<double *>(workspace(sizeof(double) * (size_t)rps * cs, kWsChunkTau)) : nullptr;
     // level-0 triangles of ALL chunks are stacked and the merge tree runs once (a merge is latency-bound: running it
     // per chunk cost 158 ms of the 1.24 s human pass)
-    const int64_t per_chunk = figh_tsqr_level0_capacity(nc);
-    double *stack = static_cast<double *>(workspace(sizeof(double) * (size_t)nchunks * per_chunk * nc * nc, 11));
+    const int64_t per_chunk = tsqr_level0_capacity(nc);
+    double *stack = static_cast<double *>(workspace(sizeof(double) * (size_t)nchunks * per_chunk * nc * nc, kWsChunkStack));
     if (!Wc || (d_tau && !tc) || !stack) return FIGH_ERR_ALLOC;
     const int nq = model->host.nq, nv = model->host.nv;
     // joint-torque regressor of single-dof joints: the rows of joint j only involve the links from j on, so the kept
     // columns in front of 14 j are exact zeros in row block j -- the structure hint of figh_tsqr_structured
     std::vector<int32_t> first;
     if (mode == FIGH_MODE_JOINT_TORQUE && nv == model->host.njoints - 1 && nc <= 80 && cs >= 64) {
-        std::vector<int32_t> cols(n);
-        if (d_col_idx) {
-            if (int rc = figh_memcpy_d2h(cols.data(), d_col_idx, sizeof(int32_t) * n)) return rc;
-        } else {
-            for (int c = 0; c < n; ++c) cols[c] = c;
-        }
+        std::vector<int32_t> cols;
+        if (int rc = host_column_list(d_col_idx, n, cols)) return rc;
         bool sorted = true;
         for (int c = 1; c < n; ++c) sorted = sorted && cols[c - 1] < cols[c];
         if (sorted) {
@@ -205,12 +205,8 @@ static int regressor_tsqr_impl(figh_model_t model, int mode, int flags, int ft_m
     int nf = 0;
     if (mode == FIGH_MODE_EXT_WRENCH && rps == 6 && model->host.njoints > 1 && model->host.jtype[1] == FIGH_JT_FREEFLYER &&
         !(flags & FIGH_FLAG_TX40) && !h_block_weight && nc > 80 && 3 * cs >= 16L * nc) {
-        std::vector<int32_t> cols(n);
-        if (d_col_idx) {
-            if (int rc = figh_memcpy_d2h(cols.data(), d_col_idx, sizeof(int32_t) * n)) return rc;
-        } else {
-            for (int c = 0; c < n; ++c) cols[c] = c;
-        }
+        std::vector<int32_t> cols;
+        if (int rc = host_column_list(d_col_idx, n, cols)) return rc;
         for (int c = 0; c < n; ++c) nf += (cols[c] % 14) >= 6;
         if (nf >= n) nf = 0;
     }
@@ -221,13 +217,13 @@ static int regressor_tsqr_impl(figh_model_t model, int mode, int flags, int ft_m
     double *tri_f = nullptr, *stack_f = nullptr, *Rf = nullptr;
     int64_t cap_f = 0;
     if (split) {
-        cap_f = figh_tsqr_level0_capacity(ncf);
-        fsel = static_cast<int *>(workspace(sizeof(int) * 2 * (size_t)n, 22));
+        cap_f = tsqr_level0_capacity(ncf);
+        fsel = static_cast<int *>(workspace(sizeof(int) * 2 * (size_t)n, kWsForceCols));
         // the force rows' level-0 triangles of ALL chunks are stacked and merged once (a merge per chunk cost 0.175 ms x 20
         // for the human model)
-        stack_f = static_cast<double *>(workspace(sizeof(double) * (size_t)ncf * ncf * cap_f * nchunks, 25));
+        stack_f = static_cast<double *>(workspace(sizeof(double) * (size_t)ncf * ncf * cap_f * nchunks, kWsChunkForceStack));
         tri_f = stack_f;
-        Rf = static_cast<double *>(workspace(sizeof(double) * (size_t)ncf * ncf, 24));
+        Rf = static_cast<double *>(workspace(sizeof(double) * (size_t)ncf * ncf, kWsForceOrBlockR));
         if (!fsel || !tri_f || !stack_f || !Rf) return FIGH_ERR_ALLOC;
         if (int rc = split_force_columns(d_cols, n, padded ? 16 : 14, fsel)) return rc;
     }
@@ -248,24 +244,27 @@ static int regressor_tsqr_impl(figh_model_t model, int mode, int flags, int ft_m
         if (d_tau)  // rows j*N + [lo, lo + nc_) of tau -> the chunk's joint-major vector (rows j*nc_ + i)
             FIGH_HIP(hipMemcpy2DAsync(tc, sizeof(double) * nc_, d_tau + lo, sizeof(double) * N, sizeof(double) * nc_, rps,
                                       hipMemcpyDeviceToDevice, stream()));
-        int64_t got = 0;
+        Level0Options torque;  // (the torque rows: all of the chunk's rows unless it is split)
         if (!first.empty() && nc_ >= 64) {
-            if (int rc = figh_tsqr_hint_begin(first.data(), rps, (int64_t)rps * nc_, n, nc)) return rc;
+            if (int rc = tile_hint(first.data(), rps, (int64_t)rps * nc_, n, nc, &torque.hint)) return rc;
         }
         const int64_t rows_f = split ? 3 * nc_ : 0;  // the chunk's force rows (row blocks 0 .. 2 of its joint-major W)
         if (split) {
             int64_t cnt_f = 0;
-            if (int rc = figh_tsqr_level0(Wc, rows_f, ldc, fsel, nf, tc, nullptr, 0, stack_f + (size_t)have_f * ncf * ncf, cap_f,
-                                          &cnt_f, nullptr))
+            if (int rc = tsqr_level0(Wc, rows_f, ldc, fsel, nf, tc, nullptr, 0, stack_f + (size_t)have_f * ncf * ncf, cap_f,
+                                     &cnt_f, nullptr))
                 return rc;
             have_f += cnt_f;
         }
-        if (chained) tsqr_level0_chain(chain_wgs, lo > 0 ? 1 : 0);
-        const int rc0 = figh_tsqr_level0(Wc + rows_f * ldc, (int64_t)rps * nc_ - rows_f, ldc, d_cols, n,
-                                         tc ? tc + rows_f : nullptr, h_block_weight, nblocks,
-                                         stack + (size_t)(chained ? 0 : have) * nc * nc, per_chunk, &got, nullptr);
-        figh_tsqr_hint_end();
-        if (rc0) return rc0;
+        if (chained) {
+            torque.chain_wgs = chain_wgs;
+            torque.chain_flags = lo > 0 ? 1 : 0;
+        }
+        int64_t got = 0;
+        if (int rc = tsqr_level0(Wc + rows_f * ldc, (int64_t)rps * nc_ - rows_f, ldc, d_cols, n, tc ? tc + rows_f : nullptr,
+                                 h_block_weight, nblocks, stack + (size_t)(chained ? 0 : have) * nc * nc, per_chunk, &got,
+                                 nullptr, torque))
+            return rc;
         have = chained ? got : have + got;
     }
     FIGH_REQUIRE(have < (1LL << 31), "too many level-0 triangles");
@@ -307,7 +306,7 @@ extern "C" int figh_regressor_tsqr_batch(figh_model_t model, int mode, int flags
         // register-tile kernel (or trajectories too short to be cut further): a launch pair per trajectory
         FIGH_REQUIRE(!(flags & FIGH_FLAG_BLOCKED_INPUTS) || n_per % 64 == 0,
                      "tile-blocked inputs: samples per trajectory must be a multiple of 64");
-        double *pair = d_R_stack ? static_cast<double *>(workspace(sizeof(double) * 2 * tri, 20)) : nullptr;
+        double *pair = d_R_stack ? static_cast<double *>(workspace(sizeof(double) * 2 * tri, kWsBatchPair)) : nullptr;
         if (d_R_stack && !pair) return FIGH_ERR_ALLOC;
         if (d_R_stack) FIGH_HIP(hipMemcpyAsync(pair, d_R_stack, sizeof(double) * tri, hipMemcpyDeviceToDevice, stream()));
         for (int64_t b = 0; b < B; ++b) {
@@ -326,11 +325,11 @@ extern "C" int figh_regressor_tsqr_batch(figh_model_t model, int mode, int flags
     const bool padded = !(model->is_chain && mode == FIGH_MODE_JOINT_TORQUE) && !(flags & FIGH_FLAG_TX40);
     const int64_t ldc = padded ? 16 * (int64_t)model->host.nlinks : ncols;
     FIGH_REQUIRE(ldc < (1L << 21), "figh_tsqr: more than 80 columns need a leading dimension below 2^21 elements");
-    double *Wc = static_cast<double *>(workspace(sizeof(double) * (size_t)rps * N_tot * ldc, 8));
+    double *Wc = static_cast<double *>(workspace(sizeof(double) * (size_t)rps * N_tot * ldc, kWsChunkW));
     if (!Wc) return FIGH_ERR_ALLOC;
     int32_t *d_cols = const_cast<int32_t *>(d_col_idx);
     if (padded) {
-        d_cols = static_cast<int32_t *>(workspace(sizeof(int32_t) * (size_t)n, 9));
+        d_cols = static_cast<int32_t *>(workspace(sizeof(int32_t) * (size_t)n, kWsChunkNormsOrCols));
         if (!d_cols) return FIGH_ERR_ALLOC;
         hipLaunchKernelGGL(pad_columns_kernel, dim3((n + 255) / 256), dim3(256), 0, stream(), d_col_idx, n, d_cols,
                            (const int *)nullptr);
@@ -345,27 +344,27 @@ extern "C" int figh_regressor_tsqr_batch(figh_model_t model, int mode, int flags
     long cap = std::min<long>({tiles / 4, (long)(rps * n_per) / (4L * nc), std::max<long>(1, 1024 / B)});
     long wgs = 1;
     while (2 * wgs <= cap) wgs *= 2;
-    double *stack = static_cast<double *>(workspace(sizeof(double) * tri * (size_t)(B * wgs), 11));
+    double *stack = static_cast<double *>(workspace(sizeof(double) * tri * (size_t)(B * wgs), kWsChunkStack));
     if (!stack) return FIGH_ERR_ALLOC;
     {
         ProfileScope scope("tsqr_batch");
         if (int rc = launch_tsqr_wide_batch(Wc, ldc, d_cols, n, nc, B, n_per, rps, N_tot, wgs, stack)) return rc;
     }
     const double *cur = stack;
-    int slot = 2;
+    WorkspaceSlot slot = kWsMergeA;
     for (long w = wgs; w > 1; w /= 2) {
         ProfileScope scope("tsqr_reduce");
         double *dst = (w == 2 && !d_R_stack) ? d_R_out : static_cast<double *>(workspace(sizeof(double) * tri * (size_t)(B * w / 2), slot));
         if (!dst) return FIGH_ERR_ALLOC;
         if (int rc = launch_tsqr_wide_pairs(cur, B * w, nc, dst)) return rc;
         cur = dst;
-        slot = slot == 2 ? 3 : 2;
+        slot = slot == kWsMergeA ? kWsMergeB : kWsMergeA;
     }
     if (!d_R_stack) {
         if (cur != d_R_out) FIGH_HIP(hipMemcpyAsync(d_R_out, cur, sizeof(double) * tri * B, hipMemcpyDeviceToDevice, stream()));
         return FIGH_OK;
     }
-    double *both = static_cast<double *>(workspace(sizeof(double) * 2 * tri * (size_t)B, 20));
+    double *both = static_cast<double *>(workspace(sizeof(double) * 2 * tri * (size_t)B, kWsBatchPair));
     if (!both) return FIGH_ERR_ALLOC;
     hipLaunchKernelGGL(interleave_stack_kernel, dim3((unsigned)((tri * B + 255) / 256)), dim3(256), 0, stream(), d_R_stack, cur,
                        (long)tri, (long)B, both);
@@ -382,7 +381,7 @@ extern "C" int figh_regressor_gram(figh_model_t model, int mode, int flags, int 
     FIGH_REQUIRE(!d_tau || (h_g && h_tau_sq), "tau given but no output for W^T tau / tau^T tau");
     const int nc = n + (d_tau ? 1 : 0);
     FIGH_REQUIRE(n >= 1 && nc <= 512, "bad column count");
-    double *d_R = static_cast<double *>(workspace(sizeof(double) * (size_t)nc * nc, 12));
+    double *d_R = static_cast<double *>(workspace(sizeof(double) * (size_t)nc * nc, kWsGramR));
     if (!d_R) return FIGH_ERR_ALLOC;
     if (int rc = figh_regressor_tsqr(model, mode, flags, ft_mask, N, d_q, d_v, d_a, d_col_idx, n, d_tau, nullptr, 0,
                                      chunk_samples, d_R))

@@ -143,7 +143,7 @@ int launch_tsqr_group(std::vector<Tsqr2Job> &jobs, int ncfull, int nfull, int cu
         }
         max_nc = J.nc > max_nc ? J.nc : max_nc;
     }
-    double *buf = static_cast<double *>(workspace(sizeof(double) * doubles, 29));
+    double *buf = static_cast<double *>(workspace(sizeof(double) * doubles, kWsGroupTri));
     if (!buf) return FIGH_ERR_ALLOC;
     {
         size_t at = 0;
@@ -165,7 +165,7 @@ int launch_tsqr_group(std::vector<Tsqr2Job> &jobs, int ncfull, int nfull, int cu
         maps.insert(maps.end(), job_of_wg[l].begin(), job_of_wg[l].end());
     }
     const size_t mb = sizeof(int) * maps.size();
-    char *dev = static_cast<char *>(workspace(jb + mb + 64, 30));
+    char *dev = static_cast<char *>(workspace(jb + mb + 64, kWsGroupJobs));
     if (!dev) return FIGH_ERR_ALLOC;
     static std::vector<char> cached;
     static const char *cached_dev = nullptr;
@@ -190,7 +190,7 @@ int launch_tsqr_group(std::vector<Tsqr2Job> &jobs, int ncfull, int nfull, int cu
     for (auto &J : jobs) max_tiles = std::max(max_tiles, (J.rows + 63) / 64);  // (enough for either tile height)
     static size_t zeroed = 0;
     const size_t zneed = sizeof(int) * (size_t)(max_tiles + 1);
-    int *zeros = static_cast<int *>(workspace(zneed, 31));
+    int *zeros = static_cast<int *>(workspace(zneed, kWsGroupZeros));
     if (!zeros) return FIGH_ERR_ALLOC;
     if (zeroed < zneed) {  // ((re)allocated: workspace() grows by 25 %)
         FIGH_HIP(hipMemsetAsync(zeros, 0, zneed, stream()));

@@ -304,11 +304,11 @@ static int launch_tree(const double *Rs, long count, int nc, int n_free, double 
     const size_t tri = sizeof(double) * (size_t)nc * nc;
     double *bufA = nullptr, *bufB = nullptr;
     if (plan.nlevels > 1) {
-        bufA = static_cast<double *>(workspace(tri * plan.nb[0], 2));
+        bufA = static_cast<double *>(workspace(tri * plan.nb[0], kWsMergeA));
         if (!bufA) return FIGH_ERR_ALLOC;
     }
     if (plan.nlevels > 2) {
-        bufB = static_cast<double *>(workspace(tri * plan.nb[1], 3));
+        bufB = static_cast<double *>(workspace(tri * plan.nb[1], kWsMergeB));
         if (!bufB) return FIGH_ERR_ALLOC;
     }
     static unsigned *counters = nullptr;

@@ -13,7 +13,7 @@ int launch_tsqr_wide_batch(const double *W, long ldw, const int *col_idx, int n,
     const long nwg = B * wgs;
     const int nch = (nc + 15) >> 4;
     const size_t blk_bytes = sizeof(double) * 256 * ((size_t)nch * (nch + 1) / 2) * (size_t)nwg;
-    double *Rblk = static_cast<double *>(workspace(blk_bytes, 13));
+    double *Rblk = static_cast<double *>(workspace(blk_bytes, kWsWideBlkOrFilter));
     if (!Rblk) return FIGH_ERR_ALLOC;
     const bool ok = wy_dispatch(wy_config(nc), [&](auto NW, auto CPW, auto NRC, auto WPE, auto LDSC) {
         hipLaunchKernelGGL((tsqr_wy_kernel<decltype(NW)::value, decltype(CPW)::value, decltype(NRC)::value,
@@ -36,7 +36,7 @@ int launch_tsqr_wide_chain(const double *W, long rows, long ldw, const int *col_
                            const double *d_blkw, long rows_per_blk, int nc, long nwg, double *Rws_out) {
     const int nch = (nc + 15) >> 4;
     const size_t blk_bytes = sizeof(double) * 256 * ((size_t)nch * (nch + 1) / 2) * (size_t)nwg;
-    double *Rblk = static_cast<double *>(workspace(blk_bytes, 13));
+    double *Rblk = static_cast<double *>(workspace(blk_bytes, kWsWideBlkOrFilter));
     if (!Rblk) return FIGH_ERR_ALLOC;
     const bool ok = wy_dispatch(wy_config(nc), [&](auto NW, auto CPW, auto NRC, auto WPE, auto LDSC) {
         FIGH_LAUNCH_TIMED((tsqr_wy_kernel<decltype(NW)::value, decltype(CPW)::value, decltype(NRC)::value,

@@ -46,7 +46,7 @@ int launch_tsqr_wide_pairs(const double *stack, long count, int nc, double *Rws_
     const long nwg = (count + 1) / 2;
     const int nch = (nc + 15) >> 4;
     const size_t blk_bytes = sizeof(double) * 256 * ((size_t)nch * (nch + 1) / 2) * (size_t)nwg;
-    double *Rblk = static_cast<double *>(workspace(blk_bytes, 13));
+    double *Rblk = static_cast<double *>(workspace(blk_bytes, kWsWideBlkOrFilter));
     if (!Rblk) return FIGH_ERR_ALLOC;
     auto launch = [&](auto NW, auto CPW, auto NRC, auto WPE, auto LDSC) {
         hipLaunchKernelGGL((tsqr_wy_kernel<decltype(NW)::value, decltype(CPW)::value, decltype(NRC)::value,
@@ -92,9 +92,9 @@ int reduce_wide_stacks(std::vector<WyPairStack> &st) {
         blk_off[j] = blk_total;
         blk_total += (size_t)256 * ((size_t)nch * (nch + 1) / 2) * (size_t)((st[j].count + 1) / 2);
     }
-    double *pp[2] = {static_cast<double *>(workspace(sizeof(double) * pp_total, 32)),
-                     static_cast<double *>(workspace(sizeof(double) * pp_total, 33))};
-    double *blk = static_cast<double *>(workspace(sizeof(double) * blk_total, 34));
+    double *pp[2] = {static_cast<double *>(workspace(sizeof(double) * pp_total, kWsStacksA)),
+                     static_cast<double *>(workspace(sizeof(double) * pp_total, kWsStacksB))};
+    double *blk = static_cast<double *>(workspace(sizeof(double) * blk_total, kWsStacksBlk));
     if (!pp[0] || !pp[1] || !blk) return FIGH_ERR_ALLOC;
     struct Level {
         std::vector<int> grouped;  // stacks of this level's grouped launch
@@ -156,7 +156,7 @@ int reduce_wide_stacks(std::vector<WyPairStack> &st) {
     const size_t tb = sizeof(WyPairJob) * table.size();
     const WyPairJob *d_table = nullptr;
     if (tb) {
-        char *devp = static_cast<char *>(workspace(tb, 35));
+        char *devp = static_cast<char *>(workspace(tb, kWsStacksJobs));
         if (!devp) return FIGH_ERR_ALLOC;
         static std::vector<char> cached;
         static const char *cached_dev = nullptr;
@@ -190,7 +190,7 @@ int reduce_wide_stacks(std::vector<WyPairStack> &st) {
 // with the pair-merge geometry -- the same latency-bound situation, eight waves and the tallest tile
 int launch_tsqr_wide_single(const double *W, long rows, long ldw, const int *col_idx, int n, int nc, double *R_out) {
     const int nch = (nc + 15) >> 4;
-    double *Rblk = static_cast<double *>(workspace(sizeof(double) * 256 * ((size_t)nch * (nch + 1) / 2), 13));
+    double *Rblk = static_cast<double *>(workspace(sizeof(double) * 256 * ((size_t)nch * (nch + 1) / 2), kWsWideBlkOrFilter));
     if (!Rblk) return FIGH_ERR_ALLOC;
     const bool ok = wy_dispatch_pair(wy_config_pair(nc), [&](auto NW, auto CPW, auto NRC, auto WPE, auto LDSC) {
         hipLaunchKernelGGL((tsqr_wy_kernel<decltype(NW)::value, decltype(CPW)::value, decltype(NRC)::value,
