@@ -10,6 +10,10 @@ reads, never by the largest entry of the problem.
 import numpy as np
 
 INT_MAX = 2 ** 10
+# column-wise backward tolerance of the TSQR kernels (test_qr_graded.py; the normal-equation terms and the per-row-block
+# residuals of test_reductions_graded.py, formed from R, share it): measured 5.2e-15 on an MI355X (rfactor 20011 x 511,
+# wide profile; 7.7e-15 with dependent columns)
+TOL_BACKWARD = 1e-13
 
 
 def int_matrix(rng, rows, n, lo=-INT_MAX, hi=INT_MAX):

@@ -627,3 +627,107 @@ def test_structured_planted_errors_rejected_columnwise_and_per_block():
     r2p[small] *= 1.0 + 1e-9
     assert np.abs(r2p - e2).max() <= 1e-9 * e2.max()
     assert not r2_ok(r2p)
+
+
+# ------------------------------------------------------------------ column norms and residual sums (test_reductions_graded.py)
+def test_reductions_colsq_ld_against_fractions():
+    """tests/reductions_common.colsq_ld (long-double column sums of squares, in row chunks) against exact rational sums of
+    the same float64 entries: relative error below m 2^-63 per column, whatever the chunking."""
+    from fractions import Fraction
+
+    import qr_graded_common as qg
+    import reductions_common as rc
+    qg.check_longdouble()  # (the 1e-300 entry and the m 2^-63 bound need an 80-bit long double)
+    rng = np.random.default_rng(11)
+    W = rng.standard_normal((53, 7)) * np.ldexp(1.0, rng.integers(-40, 40, 7))
+    W[:, 3] = 0.0
+    W[-1, 3] = 1e-300  # (the square underflows to a subnormal in float64, not in long double)
+    for chunk in (1, 10, 53, 1000):
+        got = rc.colsq_ld(W, chunk=chunk)
+        for j in range(7):
+            want = sum(Fraction(float(x)) ** 2 for x in W[:, j])
+            assert abs(Fraction(*got[j].as_integer_ratio()) - want) <= Fraction(53 * 2.0 ** -63) * want
+    assert rc.colsq_ld(np.zeros((4, 2))).tolist() == [0.0, 0.0]
+
+
+def test_reductions_gamma_and_ratio():
+    """gamma_m = m u / (1 - m u); colsq_ratio: a zero reference needs an exact zero, otherwise relative error / gamma_m."""
+    import reductions_common as rc
+    u = 2.0 ** -53
+    assert rc.gamma(1) == u / (1 - u)
+    assert rc.gamma(6 * 10 ** 6) == pytest.approx(6e6 * u, rel=1e-9)
+    assert 1e-9 > rc.gamma(6 * 10 ** 6)  # (the margin of the straddling inputs beats gamma_m up to 6e6 rows)
+    with pytest.raises(AssertionError):
+        rc.gamma(2 ** 52)
+    ref = np.array([0.0, 1.0, 2.0], dtype=np.longdouble)
+    assert rc.colsq_ratio([0.0, 1.0, 2.0], ref, 10).max() == 0.0
+    assert rc.colsq_ratio([1e-300, 1.0, 2.0], ref, 10)[0] == np.inf
+    r = rc.colsq_ratio([0.0, 1.0 + 4 * u, 2.0], ref, 10)
+    assert r[1] == pytest.approx(4 * u / rc.gamma(10), rel=1e-6) and r[1] < 1
+    assert rc.colsq_ratio([0.0, 1.0 + 2e-15, 2.0], ref, 10)[1] > 1
+
+
+@pytest.mark.parametrize("cfg", ["cfg2_ur10", "cfg4_talos"])
+def test_reductions_straddle_builder_lands_where_claimed(cfg):
+    """tests/reductions_common.straddle: inputs scaled so that the long-double sum of squares of their float64 values is
+    tol_e (1 +- 1e-9) land on the claimed side with the claimed margin in the columns oracle_np.build_regressor_basic
+    puts them in -- Ia of link k is a[:, k], fv is v[:, k], on row block k (joint torques) or on all six component rows
+    (external wrench)."""
+    from conftest import Golden
+
+    import reductions_common as rc
+    g = Golden(cfg)
+    flat = g.flat()
+    wrench = bool(g.param["is_external_wrench"])
+    N = 8 if wrench else 300
+    rng = np.random.default_rng(7)
+    q = np.repeat(g["q_big"][:1], N, axis=0)
+    v, a = rng.uniform(-2, 2, (N, int(flat["nv"]))), rng.uniform(-5, 5, (N, int(flat["nv"])))
+    param = dict(g.param, has_friction=True, has_actuator_inertia=True, has_joint_offset=False)
+    tol = 1e-6
+    claims = {}
+    for i, k in enumerate([0, 2, 3, 5]):
+        x, slot, side = (a, 10, -1) if i % 2 == 0 else (v, 11, 1)
+        side = side if i < 2 else -side
+        x[:, k], _ = rc.straddle(x[:, k], tol, side, factor=6 if wrench else 1)
+        claims[14 * k + slot] = side
+    W = oracle_np.build_regressor_basic(flat, q, v, a, param)
+    cs = rc.colsq_ld(W)
+    for c, side in claims.items():
+        rel = float((cs[c] - np.longdouble(tol)) / np.longdouble(tol))
+        assert side * rel >= 0.99e-9 and abs(rel) <= 1.01e-9, "column %d: %.3e" % (c, rel)
+    idx_e, kept = rc.exact_split(cs, tol)
+    assert {c for c, s in claims.items() if s < 0} <= set(idx_e) and {c for c, s in claims.items() if s > 0} <= set(kept)
+
+
+def test_reductions_planted_errors_rejected():
+    """Planted errors the older checks accept and the new ones reject: (1) a column-norm vector within 1e-12 of its largest
+    entry of the reference, but with one column moved across tol_e; (2) a sigma2_joint whose most precise joint is off by
+    1e-3 relative, within 1e-9 of the largest variance."""
+    import reductions_common as rc
+    # (1) TX40-like spread: max colsq 2.95e7, one column at 0.9 tol_e moved to 1.1 tol_e (2e-7 < 1e-12 * 2.95e7 = 3e-5)
+    tol = 1e-6
+    ref = np.array([2.95e7, 3.1e2, 0.9 * tol, 0.0, 1.7], dtype=np.longdouble)
+    cs = np.asarray(ref, dtype=np.float64).copy()
+    cs[2] = 1.1 * tol
+    assert rc.normwise_colsq_ok(cs, ref)
+    assert rc.colsq_ratio(cs, ref, 6 * 400).max() > 1
+    assert rc.exact_split(cs, tol)[0] != rc.exact_split(ref, tol)[0]
+    cs_zero = np.asarray(ref, dtype=np.float64).copy()
+    cs_zero[3] = 5e-6  # (a zero column reported at 5e-6: kept instead of eliminated)
+    assert rc.normwise_colsq_ok(cs_zero, ref) and rc.colsq_ratio(cs_zero, ref, 2400)[3] == np.inf
+    # (2) six joints, noise 1e-6 .. 1e-1 of a unit torque scale: sigma2 from 1e-12 to 1e-2
+    rng = np.random.default_rng(4)
+    N, nb = 500, 3
+    Wb = rng.standard_normal((6 * N, nb))
+    phi = rng.standard_normal(nb)
+    lev = np.logspace(-6, -1, 6)
+    tau = Wb @ phi + np.repeat(lev, N) * rng.standard_normal(6 * N)
+    y = np.asarray(Wb, dtype=np.longdouble) @ np.asarray(phi, dtype=np.longdouble)
+    sig2_ref = rc.sigma2_ld(tau, y, [N] * 6)
+    bound = rc.sigma2_direct_bound(tau, Wb, phi, [N] * 6, np.sqrt(sig2_ref * N))
+    sig2 = np.asarray(sig2_ref, dtype=np.float64)
+    assert (np.abs(sig2 - sig2_ref) <= bound).all()  # the float64 rounding of the reference itself passes
+    sig2[0] *= 1 + 1e-3
+    assert np.abs(sig2 - np.asarray(sig2_ref, dtype=np.float64)).max() <= 1e-9 * float(sig2_ref.max())
+    assert not (np.abs(sig2 - sig2_ref) <= bound).all()

@@ -25,7 +25,7 @@ U = 2.0 ** -53
 TOL_QR = 1e-8
 NULL_TOL = TOL_QR / 64
 # largest value measured over the whole sweep on an MI355X -> tolerance (>= 10x margin)
-TOL_BACKWARD = 1e-13  # measured 5.2e-15 (rfactor 20011 x 511, wide profile; 7.7e-15 with dependent columns)
+TOL_BACKWARD = qg.TOL_BACKWARD  # measured 5.2e-15 (rfactor 20011 x 511, wide profile; 7.7e-15 with dependent columns)
 C_FORWARD = 200.0     # forward <= C_FORWARD cond u: measured 17.6 cond u (rfactor 20011 x 511, wide)
 C_DIAG = 200.0        # diagonal <= C_DIAG cond u: measured 17.3 cond u (same case)
 
