@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # FIGH_LIB_PATH: another build of the same ABI (same-box A/B of kernel variants); default is the in-tree library
 LIB_PATH = os.environ.get("FIGH_LIB_PATH") or os.path.join(_HERE, "libfigh.so")
 
-ABI_VERSION = 106  # include/figh.h FIGH_ABI_VERSION: load() refuses a library of another ABI
+ABI_VERSION = 107  # include/figh.h FIGH_ABI_VERSION: load() refuses a library of another ABI
 
 FIGH_OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_ALLOC, ERR_UNSUPPORTED, ERR_COMM = -1, -2, -3, -4, -5
@@ -102,6 +102,8 @@ SIGNATURES = {
                                             C.c_void_p, C.c_void_p]),
     "figh_regressor_tsqr_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "figh_regressor_tsqr_batch_fused": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "figh_regressor_gram": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, _c_double_p, _c_double_p,
                                       _c_double_p]),
@@ -423,6 +425,17 @@ def regressor_tsqr_batch(model, mode, flags, ft_mask, B, n_per, d_q, d_v, d_a, d
     check(load().figh_regressor_tsqr_batch(model.handle, mode, flags, ft_mask, B, n_per, d_q.ptr, d_v.ptr, d_a.ptr,
                                            d_idx.ptr if d_idx is not None else None, n,
                                            d_R_stack.ptr if d_R_stack is not None else None, d_R.ptr))
+
+
+def regressor_tsqr_batch_fused(model, flags, B, n_per, d_q, d_v, d_a, d_idx, n, d_R_stack, d_R):
+    """regressor_tsqr_batch in one W-free launch + the merge levels (serial chains in joint-torque mode, figh.h).  Returns
+    False -- nothing launched -- when the shape is not supported; raises on any other error."""
+    rc = load().figh_regressor_tsqr_batch_fused(model.handle, flags, B, n_per, d_q.ptr, d_v.ptr, d_a.ptr, d_idx.ptr, n,
+                                                d_R_stack.ptr if d_R_stack is not None else None, d_R.ptr)
+    if rc == ERR_UNSUPPORTED:
+        return False
+    check(rc)
+    return True
 
 
 def regressor_gram(model, mode, flags, ft_mask, N, d_q, d_v, d_a, d_idx, n, d_tau=None, chunk_samples=0):

@@ -29,6 +29,21 @@
 // Hence two producers with a buffer each: 2 x 44 KB tiles + 2 x 9 KB staging + C x 7.4 KB triangles = 152 KB (C = 6).
 // All arithmetic is fp64.  The kept-column list is the caller's (the previous pass's, verified afterwards against the
 // norms this launch produces -- the same speculation figh_tsqr_selected makes with the column count).
+//
+// ---- the batched, W-free form (figh_regressor_tsqr_batch_fused): the excitation objective np.linalg.cond(W_b) of
+// examples/tiago/optimal_trajectory.py:100-133 at the B perturbed trajectories of one finite-difference gradient (:296-313)
+// needs B small triangles and nothing else.  The same kernel, template flag TRAJ: grid (S, B), workgroup (s, b) owns the
+// sample tiles s, s + S, ... of trajectory b (a tile never straddles two trajectories; the last one of a trajectory is the
+// ragged tile body), the producers neither stream W out nor accumulate norms.  Every workgroup leaves its consumers'
+// triangles; fused_batch_merge_kernel then factors the S x ncons triangles of every trajectory in one launch per level
+// (grid (workgroups per trajectory, B): tsqr_coop_kernel's sweep, 512 stacked rows per workgroup), so the launch count is
+// 1 + levels whatever B is -- one level up to 512 stacked rows (UR10: S <= 2), two up to 512 * 512 / nc, never more than
+// three.  The triangle of the previous trajectories (d_R_stack) is APPENDED to every trajectory's stack: the first merge
+// level reads it in place as the nc rows behind the trajectory's own -- no copy, no launch, and the level-0 kernel keeps
+// one code path (seeding a consumer would need the triangle in the packed LDS + register form of Tsqr2State).
+// Merging inside the level-0 kernel when S == 1 was not built: it would save one launch of ~40 column steps' latency but
+// needs a workgroup barrier between roles that never meet at one.
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <type_traits>
@@ -92,7 +107,11 @@ struct FusedGeom {
     static constexpr int CONS0 = NPROD * PSIZE;
 };
 
-template <int NJ>
+// TRAJ (figh_regressor_tsqr_batch_fused): grid (S, B) -- workgroup (s, b) walks the sample tiles s, s + S, ... of trajectory
+// b, whose N samples start at sample b N of q, v, a.  The producers only emit and announce tiles: W, tau, colsq_part are
+// unused (no stream-out, no column norms), nc == n.  Everything else -- tile order, claims, column steps -- is the code of
+// the identification launch, which TRAJ = false leaves exactly as it was.
+template <int NJ, bool TRAJ = false>
 __global__ __launch_bounds__(512) void fused_chain_tsqr_kernel(
     const ChainParams<NJ> P, const int flags, const long N, const double *__restrict__ q, const double *__restrict__ v,
     const double *__restrict__ a, double *__restrict__ W, const double *__restrict__ tau, const int *__restrict__ col_idx,
@@ -106,6 +125,14 @@ __global__ __launch_bounds__(512) void fused_chain_tsqr_kernel(
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const long ntiles_s = (N + 63) / 64;  // sample tiles
     const long b = blockIdx.x, Gd = gridDim.x;
+    long wg = b;  // this workgroup's place in Rws
+    if constexpr (TRAJ) {
+        const long first = (long)blockIdx.y * N * NJ;  // the trajectory's samples
+        q += first;
+        v += first;
+        a += first;
+        wg = (long)blockIdx.y * Gd + b;
+    }
     // this workgroup's sample tiles: b, b + Gd, ...; producer p takes every other one, starting with its p-th
     const long count_s = b < ntiles_s ? (ntiles_s - b + Gd - 1) / Gd : 0;
     const int T0 = (int)(((count_s + 1) / 2) * NJ), T1 = (int)((count_s / 2) * NJ);  // row tiles of producer 0 / 1
@@ -141,7 +168,7 @@ __global__ __launch_bounds__(512) void fused_chain_tsqr_kernel(
                     pqd[k] = v[is * NJ + k];
                     pqdd[k] = a[is * NJ + k];
                 }
-                if (tau) {
+                if (!TRAJ && tau) {
 #pragma unroll
                     for (int j = 0; j < NJ; ++j) {
                         const double tv = tau[(long)j * N + is];
@@ -274,9 +301,10 @@ __global__ __launch_bounds__(512) void fused_chain_tsqr_kernel(
 #pragma unroll
                     for (int c = 0; c < 14; ++c) dst[c] = live ? o[c] : 0.0;
                 }
-                my[NC] = tau ? stau[64 * j + lane] : 0.0;
+                if constexpr (!TRAJ) my[NC] = tau ? stau[64 * j + lane] : 0.0;  // (TRAJ: nc == n, the slot is never gathered)
                 lds_post(&ctrl->produced, t + 1);
                 ++t;
+                if constexpr (TRAJ) continue;  // no W: the tile lives and dies in LDS
 
                 // ---- stream the 64 x NC tile to W rows j*N+i0 .. : one contiguous run (the launcher guarantees ldw == NC and
                 // 16-byte alignment).  Chunk id (16 B) sits at byte 16 id in W and at 16 (id + r) in the padded tile,
@@ -372,7 +400,8 @@ __global__ __launch_bounds__(512) void fused_chain_tsqr_kernel(
             else sample_tile(std::false_type{}, s);
         }
         asm volatile("" ::: "memory");
-        for (int c = lane; c < NC; c += 64) colsq_part[(b * G::NPROD + wave) * NC + c] = cacc[c];
+        if constexpr (!TRAJ)
+            for (int c = lane; c < NC; c += 64) colsq_part[(b * G::NPROD + wave) * NC + c] = cacc[c];
         return;
     }
     // ======================================================================================================= consumers
@@ -488,7 +517,7 @@ __global__ __launch_bounds__(512) void fused_chain_tsqr_kernel(
         tsqr2_panels<0, NCC, NRC, false, true>(S, first_nz, [](auto) {});
     }
     // this wave's triangle (compact nc x nc, row-major): the LDS chunks, then the register chunk
-    double *Rg = Rws + ((long)b * ncons + c_id) * (long)nc * nc;
+    double *Rg = Rws + (wg * ncons + c_id) * (long)nc * nc;
     const int nlds = 16 * LCH - pad;  // columns of the compact triangle that live in LDS
     for (int e = lane; e < nc * nc; e += 64) {
         const int k = e / nc, col = e - k * nc;
@@ -523,11 +552,50 @@ __global__ __launch_bounds__(256) void fused_reduce_partials_kernel(const double
     if (threadIdx.x == 0) out[c] = sm[0];
 }
 
+// One merge level of the batched form: workgroup (bl, b) factors the stacked rows [512 bl, 512 (bl + 1)) of trajectory b's
+// input -- `rows` rows of its own triangles (Rs + b * rows * nc), then, when `extra` is given, the nc rows of that
+// triangle, the same for every trajectory -- into triangle bl of the trajectory's gridDim.x outputs.  tsqr_coop_kernel<4, 8>
+// (figh_linalg.hip) with a trajectory index; the zero fill leaves exact zeros below the diagonal.
+__global__ __launch_bounds__(512) void fused_batch_merge_kernel(const double *__restrict__ Rs, const long rows,
+                                                                const double *__restrict__ extra, const int nc,
+                                                                double *__restrict__ Rout) {
+    constexpr int NCC = 4, NW = 8;
+    __shared__ double pw[2][NW][16 * NCC];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane_c = lane & 15, lane_g = lane >> 4;
+    const long r0 = ((long)blockIdx.x * NW + wave) * 64;
+    const int pad = 16 * NCC - nc;
+    const double *mine = Rs + (long)blockIdx.y * rows * nc;
+    const long rows_all = rows + (extra ? nc : 0);
+    double *Rg = Rout + ((long)blockIdx.y * gridDim.x + blockIdx.x) * nc * nc;
+    for (int e = threadIdx.x; e < nc * nc; e += 64 * NW) Rg[e] = 0.0;
+    double T[NCC][16];
+#pragma unroll
+    for (int cc = 0; cc < NCC; ++cc)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const long row = r0 + 16 * (i >> 2) + lane_g + 4 * (i & 3);
+            const int col = 16 * cc + lane_c - pad;
+            const bool ok = row < rows_all && col >= 0;
+            const double *src = row < rows ? mine + row * nc : extra + (row - rows) * nc;
+            const double v = ok ? src[col] : 0.0;
+            T[cc][i] = v;
+        }
+    __syncthreads();  // the zero fill of Rg is ordered before the row stores of wave 0 (same workgroup)
+    tsqr_coop_panels<0, NCC, NW>(T, nc, pad, lane_c, lane_g, wave, pw, Rg);
+}
+
 static size_t fused_tri_doubles(int nc) {  // LDS per consumer: 64 + 16 doubles of scratch + the three LDS chunks of the triangle
     const int pad = 64 - nc;
     size_t skip = 0;
     for (int kp = 0; kp < pad; ++kp) skip += 16 * (3 - (kp >> 4) > 0 ? 3 - (kp >> 4) : 0);
     return 80 + 256 * (size_t)(3 + 2 + 1) - skip;
+}
+
+// consumer waves per workgroup: what fits behind the `fixed` doubles of the producers in 160 KB of LDS, at most six
+static int fused_consumers(size_t fixed, size_t tri) {
+    const size_t budget = (160 * 1024) / sizeof(double);
+    return (int)std::min<size_t>(6, (budget - fixed) / tri);
 }
 
 template <int NJ>
@@ -541,9 +609,7 @@ static int launch_fused(const figh_model_s *m, int flags, long N, const double *
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     const size_t tri = fused_tri_doubles(nc);
     const size_t fixed = (size_t)G::CONS0;
-    const size_t budget = (160 * 1024) / sizeof(double);
-    int ncons = (int)((budget - fixed) / tri);
-    if (ncons > 6) ncons = 6;
+    const int ncons = fused_consumers(fixed, tri);
     if (ncons < 3) {
         set_error("fused regressor + TSQR: the triangles of three consumer waves do not fit next to the tile");
         return FIGH_ERR_UNSUPPORTED;
@@ -572,6 +638,70 @@ static int launch_fused(const figh_model_s *m, int flags, long N, const double *
     *Rws_out = Rws;
     *count_out = grid * ncons;
     return FIGH_OK;
+}
+
+// Slices per trajectory of the batched launch.  One workgroup occupies a CU (152 KB of LDS), so B workgroups fill the chip
+// when B >= CUs: S = 1, a trajectory is one workgroup and its merge one level.  Below that a trajectory is cut into
+// S = CUs / B slices (rounded down: one round of the chip), at most one per sample tile -- a slice of a single tile leaves
+// producer 1 idle, which costs less than a CU that has no workgroup at all.  (tests/test_objective_batch_fused.py mirrors it.)
+static long fused_batch_slices(long B, long n_per, int cus) {
+    const long tiles = (n_per + 63) / 64;
+    return std::max(1L, std::min(tiles, (long)cus / B));
+}
+
+template <int NJ>
+static int launch_fused_batch(const figh_model_s *m, int flags, long B, long n_per, const double *q, const double *v,
+                              const double *a, const int *d_cols, int n, const double *d_R_stack, double *d_R_out) {
+    using G = FusedGeom<NJ>;
+    const int nc = n;
+    int dev = 0, cus = 256;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const size_t tri = fused_tri_doubles(nc);
+    const size_t fixed = (size_t)G::CONS0;
+    const int ncons = fused_consumers(fixed, tri);
+    if (ncons < 3) {
+        set_error("fused batch regressor + TSQR: the triangles of three consumer waves do not fit next to the tile");
+        return FIGH_ERR_UNSUPPORTED;
+    }
+    const long S = fused_batch_slices(B, n_per, cus);
+    const size_t lds = sizeof(double) * (fixed + (size_t)ncons * tri);
+    static bool attr_set[16] = {};
+    if (!attr_set[NJ]) {
+        FIGH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fused_chain_tsqr_kernel<NJ, true>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        attr_set[NJ] = true;
+    }
+    const size_t tsz = sizeof(double) * (size_t)nc * nc;
+    double *Rws = static_cast<double *>(workspace(tsz * (size_t)(B * S * ncons), kWsFusedBatchTri));
+    if (!Rws) return FIGH_ERR_ALLOC;
+    const ChainParams<NJ> P = chain_params<NJ>(m);
+    {
+        ProfileScope scope("fused_chain_tsqr_batch", true);
+        FIGH_LAUNCH_TIMED((fused_chain_tsqr_kernel<NJ, true>), dim3((unsigned)S, (unsigned)B), dim3(64 * (G::NPROD + ncons)),
+                          lds, P, flags, n_per, q, v, a, (double *)nullptr, (const double *)nullptr, d_cols, n, nc,
+                          (double *)nullptr, Rws, ncons, (int)tri, null_pivot_sq());
+    }
+    FIGH_HIP(hipGetLastError());
+    // merge levels: cnt triangles per trajectory (+ d_R_stack at the first level) -> ceil(rows / 512) -> ... -> 1
+    const double *cur = Rws, *extra = d_R_stack;
+    long cnt = S * ncons;
+    WorkspaceSlot slot = kWsMergeA;
+    for (;;) {
+        ProfileScope scope("tsqr_reduce");
+        const long rows = cnt * nc;
+        const long nb = (rows + (extra ? nc : 0) + 511) / 512;
+        double *dst = nb == 1 ? d_R_out : static_cast<double *>(workspace(tsz * (size_t)(B * nb), slot));
+        if (!dst) return FIGH_ERR_ALLOC;
+        hipLaunchKernelGGL(fused_batch_merge_kernel, dim3((unsigned)nb, (unsigned)B), dim3(512), 0, stream(), cur, rows, extra,
+                           nc, dst);
+        FIGH_HIP(hipGetLastError());
+        if (nb == 1) return FIGH_OK;
+        cur = dst;
+        cnt = nb;
+        extra = nullptr;
+        slot = slot == kWsMergeA ? kWsMergeB : kWsMergeA;
+    }
 }
 
 }  // namespace figh
@@ -614,4 +744,49 @@ extern "C" int figh_regressor_tsqr_fused(figh_model_t model, int flags, int64_t 
     }
     if (rc) return rc;
     return tsqr_reduce_stack(Rws, count, nc, n, tol_qr, d_R_out);
+}
+
+// The smallest trajectory the batched launch takes: one full sample tile.  64 samples are at least 320 rows, more than the
+// nc + 8 <= 72 rows from which level 0 applies the null-pivot rule, so a trajectory's triangle never depends on whether a
+// consumer happened to see enough of its rows; shorter trajectories are mostly masked lanes and keep the two-launch path.
+static constexpr int64_t kFusedBatchMinSamples = 64;
+
+extern "C" int figh_regressor_tsqr_batch_fused(figh_model_t model, int flags, int64_t B, int64_t n_per, const double *d_q,
+                                               const double *d_v, const double *d_a, const int32_t *d_col_idx, int n,
+                                               const double *d_R_stack, double *d_R_out) {
+    FIGH_REQUIRE(model && d_q && d_v && d_a && d_col_idx && d_R_out, "NULL pointer");
+    FIGH_REQUIRE(B >= 1 && n_per >= 1 && n >= 1, "figh_regressor_tsqr_batch_fused: at least one trajectory, sample and column");
+    const DevModel &h = model->host;
+    if (!model->is_chain || h.nlinks < 5 || h.nlinks > 7) {
+        // (eight links: two 58 KB tile buffers leave 17 KB of the 160 KB of LDS, less than three consumer triangles)
+        set_error("fused batch regressor + TSQR: serial chains of 5 to 7 joints (LDS: two tile buffers + three consumer triangles)");
+        return FIGH_ERR_UNSUPPORTED;
+    }
+    if (flags & (FIGH_FLAG_TX40 | FIGH_FLAG_GENERIC | FIGH_FLAG_BLOCKED_INPUTS)) {
+        set_error("fused batch regressor + TSQR: joint-torque mode of the chain kernel only (no TX40 coupling, generic kernel or "
+                  "tile-blocked inputs)");
+        return FIGH_ERR_UNSUPPORTED;
+    }
+    if (n > 64) {
+        set_error("fused batch regressor + TSQR: at most 64 columns");
+        return FIGH_ERR_UNSUPPORTED;
+    }
+    if (n_per < kFusedBatchMinSamples) {
+        set_error("fused batch regressor + TSQR: at least 64 samples (one full sample tile) per trajectory");
+        return FIGH_ERR_UNSUPPORTED;
+    }
+    if (B > 65535) {
+        set_error("fused batch regressor + TSQR: at most 65535 trajectories (one grid row each)");
+        return FIGH_ERR_UNSUPPORTED;
+    }
+    if (int rc = ensure_device()) return rc;
+    const int f = flags & 7;
+    switch (h.nlinks) {
+        case 5:
+            return launch_fused_batch<5>(model, f, (long)B, (long)n_per, d_q, d_v, d_a, d_col_idx, n, d_R_stack, d_R_out);
+        case 6:
+            return launch_fused_batch<6>(model, f, (long)B, (long)n_per, d_q, d_v, d_a, d_col_idx, n, d_R_stack, d_R_out);
+        default:
+            return launch_fused_batch<7>(model, f, (long)B, (long)n_per, d_q, d_v, d_a, d_col_idx, n, d_R_stack, d_R_out);
+    }
 }

@@ -79,7 +79,7 @@ LaunchEvents take_launch_events();  // the pair of the innermost at_launch scope
 enum WorkspaceSlot {
     kWsRegressorNorms,      // per-workgroup diag(W^T W) partials: chain and tree regressor kernels, fused chain TSQR
     kWsColsqParts,          // figh_colsq's per-block partials
-    kWsMergeA,              // merge-level outputs, ping: tsqr_reduce, launch_tsqr_tree, figh_regressor_tsqr_batch
+    kWsMergeA,              // merge-level outputs, ping: tsqr_reduce, launch_tsqr_tree, figh_regressor_tsqr_batch[_fused]
     kWsMergeB,              // ... pong
     kWsBlockWeights,        // tsqr_level0: the row-block weights
     kWsLevel0TriOrWrench,   // level-0 triangles: tsqr_level0 without a caller buffer, figh_fused.hip, the wrench torque stack
@@ -115,6 +115,7 @@ enum WorkspaceSlot {
     kWsBlocksWideTri,       // figh_tsqr_selected_blocks: level-0 triangles of the wide blocks
     kWsLinkPos,             // regressor_tsqr_impl: the link map of the link-compact layout
     kWsBlocksMidTri,        // figh_tsqr_selected_blocks: level-0 triangles of the mid blocks
+    kWsFusedBatchTri,       // figh_regressor_tsqr_batch_fused: the consumers' triangles of every workgroup
     kWorkspaceSlots
 };
 

@@ -57,8 +57,13 @@ def objective_cond(robot, q, v, a, param, idx_e, idx_base, R_stack=None, couplin
 
 
 def base_regressor_triangles_batch(robot, trajectories, param, idx_e, idx_base, R_stack=None, coupling=False):
-    """R factors (B x r x r) of the base regressors of B trajectories ``[(q_b, v_b, a_b), ...]`` of equal length -- one
-    K1 launch over all samples and one batched TSQR launch (``figh_regressor_tsqr_batch``) instead of B launch pairs."""
+    """R factors (B x r x r) of the base regressors of B trajectories ``[(q_b, v_b, a_b), ...]`` of equal length.
+
+    Serial chains of 5 to 7 joints in joint-torque mode (UR10), r <= 64, at least 64 samples per trajectory: one launch
+    that builds and factors every trajectory's regressor tiles in LDS, W never stored, + one to three merge launches,
+    whatever B is (``figh_regressor_tsqr_batch_fused``).  Everything else goes through ``figh_regressor_tsqr_batch``: more
+    than 80 base columns (TIAGo, TALOS) in one K1 launch over all samples, one batched TSQR launch and the pair-merge
+    levels; up to 80 columns (TX40 with its coupling columns, short trajectories) trajectory by trajectory."""
     if len(trajectories) == 0:
         raise ValueError("no trajectory given")
     mode, flags, ft_mask = regressor_flags(param, coupling)
@@ -82,7 +87,10 @@ def base_regressor_triangles_batch(robot, trajectories, param, idx_e, idx_base, 
             raise ValueError("R_stack must be the %d x %d triangle of the previous base regressor" % (r, r))
         d_stack = _lib.DeviceArray.from_host(np.triu(R_stack).reshape(-1))
     d_R = _lib.DeviceArray((B * r * r,), np.float64)
-    _lib.regressor_tsqr_batch(dm, mode, flags, ft_mask, B, n_per, d_q, d_v, d_a, d_idx, r, d_stack, d_R)
+    fused = (mode == _lib.MODE_JOINT_TORQUE and dm.is_chain()
+             and _lib.regressor_tsqr_batch_fused(dm, flags, B, n_per, d_q, d_v, d_a, d_idx, r, d_stack, d_R))
+    if not fused:  # (ERR_UNSUPPORTED: nothing was launched)
+        _lib.regressor_tsqr_batch(dm, mode, flags, ft_mask, B, n_per, d_q, d_v, d_a, d_idx, r, d_stack, d_R)
     return np.triu(d_R.to_host().reshape(B, r, r))
 
 

@@ -91,7 +91,7 @@ typedef struct figh_model_s *figh_model_t;
  * (round 5 did so for figh_tsqr_selected_wrench / figh_regressor_build_padded without a bump: a library of the older ABI
  * accepts the longer argument list under cdecl and silently ignores the new arguments).  figaroh_plus_amd/_lib.py refuses a
  * library -- in-tree or FIGH_LIB_PATH -- whose figh_version() differs from the value it was written against. */
-#define FIGH_ABI_VERSION 106
+#define FIGH_ABI_VERSION 107
 int figh_version(void);
 const char *figh_last_error(void);
 int figh_device_count(int *count);
@@ -381,6 +381,22 @@ int figh_regressor_tsqr_norms(figh_model_t model, int mode, int flags, int ft_ma
 int figh_regressor_tsqr_batch(figh_model_t model, int mode, int flags, int ft_mask, int64_t B, int64_t n_per,
                               const double *d_q, const double *d_v, const double *d_a, const int32_t *d_col_idx, int n,
                               const double *d_R_stack, double *d_R_out);
+/* figh_regressor_tsqr_batch_fused: figh_regressor_tsqr_batch (same inputs, same B plain n x n triangles with zeros below the
+ * diagonal, d_R_stack folded in when given) for fixed-base serial chains in joint-torque mode, in ONE launch that never
+ * writes W: workgroup (slice s, trajectory b) builds the regressor rows of its 64-sample tiles of trajectory b in LDS
+ * (build_regressor_basic, regressor.py:20-194, the pin.computeJointTorqueRegressor loop :45-87) and factors the columns
+ * d_col_idx (build_regressor_reduced + build_baseRegressor) there -- the np.linalg.cond(W_b) of objective_func
+ * (examples/tiago/optimal_trajectory.py:100-133) needs only the triangle of W_b -- then one launch per merge level (at most
+ * three, one when a trajectory is one workgroup) turns every trajectory's triangles + d_R_stack (np.vstack((W_stack, W_b)))
+ * into d_R_out[b].  The launch count does not depend on B; the slices per trajectory are chosen so that B * S workgroups
+ * fill the chip.  d_col_idx is required.  Tiles go to whichever consumer wave is free: the triangles are reproduced up to
+ * rounding from run to run.  FIGH_ERR_UNSUPPORTED (nothing launched, figh_last_error says which): not a serial chain of
+ * 5 to 7 joints; FIGH_FLAG_TX40, FIGH_FLAG_GENERIC or FIGH_FLAG_BLOCKED_INPUTS; n > 64, or n = 64 with 7 joints (LDS: two
+ * tile buffers leave room for fewer than three consumer triangles); n_per < 64 (one full sample tile:
+ * 64 samples are more rows than the nc + 8 from which level 0 applies the null-pivot rule); B > 65535. */
+int figh_regressor_tsqr_batch_fused(figh_model_t model, int flags, int64_t B, int64_t n_per, const double *d_q,
+                                    const double *d_v, const double *d_a, const int32_t *d_col_idx, int n,
+                                    const double *d_R_stack, double *d_R_out);
 /* figh_regressor_gram: h_G = W_e^T W_e (n x n, row-major, host), h_g = W_e^T tau (n), *h_tau_sq = tau^T tau, formed
  * from the Householder R (G = R1^T R1): the normal-equation quantities of the SIP QP (identification_tools.py:528-531)
  * and of the weighted LS statements (staubli_TX40/identification.py:320-327).  h_g / h_tau_sq may be NULL iff d_tau

@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Batched excitation objective: B trajectories of n_per samples of one finite-difference gradient
 through objective_cond_batch against B calls of objective_cond, TIAGo (cfg3 fixture) by default.  Prints the wall time of
-the Python calls (host arrays in, floats out) and of the device part alone (samples already in HBM)."""
+the Python calls (host arrays in, floats out) and of the device part alone (samples already in HBM).
+
+    objective_batch_bench.py [fixture model [n_per]] [--entry=batch|fused]
+
+--entry selects the C entry the device part times: figh_regressor_tsqr_batch (default; the only one before ABI 107) or
+figh_regressor_tsqr_batch_fused (serial chains, e.g. ``cfg2_ur10 ur10 1000``: profiles/objective_batch_chain.json).  The
+Python call always is the public objective_cond_batch, whatever it dispatches to."""
 import json
 import os
 import sys
@@ -17,15 +23,24 @@ from figaroh_plus_amd.tools.randomdata import sample_inputs  # noqa: E402
 from figaroh_plus_amd.tools.regressor import regressor_flags  # noqa: E402
 from figaroh_plus_amd.tools.robot import Robot  # noqa: E402
 
-fixture, model = (sys.argv[1], sys.argv[2]) if len(sys.argv) > 2 else ("cfg3_tiago", "tiago")
-n_per = int(sys.argv[3]) if len(sys.argv) > 3 else 2000
+entry = "batch"
+args = []
+for arg in sys.argv[1:]:
+    if arg.startswith("--entry="):
+        entry = arg.split("=", 1)[1]
+    else:
+        args.append(arg)
+if entry not in ("batch", "fused"):
+    sys.exit("--entry=batch or --entry=fused")
+fixture, model = (args[0], args[1]) if len(args) > 1 else ("cfg3_tiago", "tiago")
+n_per = int(args[2]) if len(args) > 2 else 2000
 meta = json.load(open(os.path.join(ROOT, "tests", "golden", fixture + ".json")))
 z = np.load(os.path.join(ROOT, "tests", "golden", fixture + ".npz"))
 robot = Robot.from_flat(model)
 param, idx_e, idx_base = meta["param"], z["idx_e"], z["idx_base"]
 rng = np.random.default_rng(0)
-report = {"model": model, "n_per": n_per, "base_columns": int(len(idx_base)), "rows": []}
-for B in (1, 8, 64):
+report = {"model": model, "n_per": n_per, "base_columns": int(len(idx_base)), "device_entry": entry, "rows": []}
+for B in (1, 8, 64, 256):  # (256: a central-difference gradient over 6 joints x ~20 waypoints)
     trajs = [sample_inputs(robot.model, n_per, rng, 1.5, 2, 5) for _ in range(B)]
     for _ in range(2):
         got = objective_cond_batch(robot, trajs, param, idx_e, idx_base, coupling=meta["coupling"])
@@ -49,7 +64,11 @@ for B in (1, 8, 64):
     for _ in range(7):
         _lib.synchronize()
         t0 = time.perf_counter()
-        _lib.regressor_tsqr_batch(dm, mode, flags, ft_mask, B, n_per, d[0], d[1], d[2], d_idx, r, None, d_R)
+        if entry == "fused":
+            if not _lib.regressor_tsqr_batch_fused(dm, flags, B, n_per, d[0], d[1], d[2], d_idx, r, None, d_R):
+                sys.exit("figh_regressor_tsqr_batch_fused does not take this shape")
+        else:
+            _lib.regressor_tsqr_batch(dm, mode, flags, ft_mask, B, n_per, d[0], d[1], d[2], d_idx, r, None, d_R)
         _lib.synchronize()
         ts.append(time.perf_counter() - t0)
     row = {"B": B, "batch_call_ms": 1e3 * t_batch, "sequential_calls_ms": 1e3 * t_seq, "device_batch_ms": 1e3 * float(np.median(ts[2:])),
