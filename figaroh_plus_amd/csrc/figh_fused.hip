@@ -186,7 +186,7 @@ __global__ __launch_bounds__(512) void fused_chain_tsqr_kernel(
 #pragma unroll
                 for (int k = 0; k < NJ; ++k) {
                     double s_, c_;
-                    sincos(pq[k], &s_, &c_);
+                    sincos_angle(pq[k], &s_, &c_);
                     cs[k] = c_;
                     sn[k] = s_;
                     double Rj[9], R[9];

@@ -85,7 +85,7 @@ __global__ __launch_bounds__(64) void regressor_chain_kernel(const ChainParams<N
                 qd[k] = pqd[k];
                 qdd[k] = pqdd[k];
                 double s, c;
-                sincos(qk, &s, &c);
+                sincos_angle(qk, &s, &c);
                 double Rj[9];
                 rodrigues(P.axis[k], c, s, Rj);
                 matmul3(P.Rp[k], Rj, R[k]);

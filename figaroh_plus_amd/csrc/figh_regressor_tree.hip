@@ -295,7 +295,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FC ? 1 : 2))
                 if (jt == FIGH_JT_REVOLUTE || jt == FIGH_JT_CONTINUOUS) {
                     double s, c;
                     if (jt == FIGH_JT_REVOLUTE) {
-                        sincos(jq0, &s, &c);
+                        sincos_angle(jq0, &s, &c);
                     } else {
                         c = jq0;
                         s = jq1;

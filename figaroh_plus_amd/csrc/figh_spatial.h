@@ -41,6 +41,20 @@ __device__ __forceinline__ void matmul3(const double *A, const double *B, double
 }
 __device__ __forceinline__ double sgn(double x) { return (double)((x > 0.0) - (x < 0.0)); }
 
+// sin and cos of a joint angle.  Below 2^30 this is the device library's sincos of x itself (n = 0: the FMAs return x).
+// From 2^30 on the library switches to another argument reduction, whose result on gfx950 was measured off by about
+// |x| 2^-53 -- 1e-4 at 2^40 rad, every entry of W behind that joint with it (tests/test_regressor_entrywise.py, regime
+// bigq).  Angles from 2^30 to 2^45 are therefore reduced here, x - n 2 pi with 2 pi as the sum of two doubles and one
+// rounding per FMA: the reduced angle is good to 7e-16 absolutely, which is what the rotation entries are worth anyway.
+// Branch-free and two temporaries, so that the kernels keep their register allocation.  Larger angles go to the
+// library as they are.
+__device__ __forceinline__ void sincos_angle(double x, double *s, double *c) {
+    const double ax = fabs(x);
+    const double n = (ax >= 0x1p30 && ax < 0x1p45) ? rint(x * 0x1.45f306dc9c883p-3) : 0.0;
+    const double r = fma(-n, 0x1.1a62633145c07p-52, fma(-n, 0x1.921fb54442d18p+2, x));
+    sincos(r, s, c);
+}
+
 // J^T B for the body regressor B = bodyRegressor(v, a) of one link and a motion axis J = (Jl, Ja) expressed in the
 // link frame, in closed form -- the ten entries of one row of pin.computeJointTorqueRegressor for that link, in
 // FIGAROH's column order [Ixx Ixy Ixz Iyy Iyz Izz mx my mz m] (regressor.py:73-82).  acc = a_lin + w x v_lin,
