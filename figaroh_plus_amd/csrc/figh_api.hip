@@ -75,6 +75,16 @@ int ensure_device() {
     return FIGH_OK;
 }
 
+int cu_count() {
+    static int cus = 0;
+    if (!cus) {
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    }
+    return cus;
+}
+
 void *workspace(size_t bytes, WorkspaceSlot slot) {
     if (bytes <= g_ws_bytes[slot]) return g_ws[slot];
     if (g_ws[slot]) {

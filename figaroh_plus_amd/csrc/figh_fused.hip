@@ -46,6 +46,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <string>
 #include <type_traits>
 
 #include "figh_internal.h"
@@ -90,6 +91,12 @@ __device__ __forceinline__ double opaque_v(double x) {
     asm volatile("" : "+v"(x));
     return x;
 }
+
+// Row block of the jo-th row tile of a sample tile: 0, NJ-1, 1, NJ-2, ... -- a row block of joint 1 costs a consumer ten
+// times what one of joint 6 costs (104 against 11 chunk-steps for UR10), and with only one tile of slack per producer the
+// consumers would all be busy during the heavy half of a sample tile and all be waiting during the light half.
+template <int NJ>
+constexpr int fused_row_of(int jo) { return (jo & 1) ? NJ - 1 - (jo >> 1) : (jo >> 1); }
 
 template <int NJ>
 struct FusedGeom {
@@ -180,7 +187,8 @@ __global__ __launch_bounds__(512) void fused_chain_tsqr_kernel(
                     sqd[64 * (2 * k) + lane] = pqd[k];
                     sqd[64 * (2 * k + 1) + lane] = pqdd[k];
                 }
-                // forward recursion (regressor_chain_kernel, statement for statement)
+                // forward recursion (regressor_chain_kernel, statement for statement -- and kept as text in both kernels: as an
+                // inlined helper it moved the register allocation of either, see the note at the row entries below)
                 double vl[3] = {0, 0, 0}, om[3] = {0, 0, 0}, da[3] = {0, 0, 0};
                 double al[3] = {opaque_v(-P.g[0]), opaque_v(-P.g[1]), opaque_v(-P.g[2])};
 #pragma unroll
@@ -229,12 +237,7 @@ __global__ __launch_bounds__(512) void fused_chain_tsqr_kernel(
             }
 #pragma unroll
             for (int jo = 0; jo < NJ; ++jo) {
-                // Row order 0, NJ-1, 1, NJ-2, ...: a row block of joint 1 costs a consumer ten times what one of joint 6 costs
-                // (104 against 11 chunk-steps for UR10), and with only one tile of slack per producer the consumers would
-                // all be busy during the heavy half of a sample tile and all be waiting during the light half.
-                const int j = (jo & 1) ? NJ - 1 - (jo >> 1) : (jo >> 1);
-                const int jprev = jo == 0 ? (((NJ - 1) & 1) ? NJ - 1 - ((NJ - 1) >> 1) : ((NJ - 1) >> 1))
-                                          : (((jo - 1) & 1) ? NJ - 1 - ((jo - 1) >> 1) : ((jo - 1) >> 1));
+                const int j = fused_row_of<NJ>(jo), jprev = fused_row_of<NJ>(jo == 0 ? NJ - 1 : jo - 1);
                 // the buffer is free once the previous tile has been gathered by its consumer (this wave's own reads of it
                 // -- stream-out, column norms -- are behind it in program order)
                 while (lds_peek(&ctrl->taken) < t) __builtin_amdgcn_s_sleep(1);
@@ -269,6 +272,10 @@ __global__ __launch_bounds__(512) void fused_chain_tsqr_kernel(
                             Ja[d] = nJa[d];
                         }
                     }
+                    // (not axis_times_body_regressor, figh_spatial.h, which regressor_chain_kernel calls: through it another
+                    // product of each sum is contracted into the FMA here and W changes by one rounding.  The forward step and
+                    // the row-block recursion are hand copies for a like reason: as shared inlined helpers they changed VGPR
+                    // and spill counts of this kernel and of regressor_chain_kernel, profiles/dedupe_ab.txt)
                     double o[14];
                     o[9] = Jl[0] * acc[k][0] + Jl[1] * acc[k][1] + Jl[2] * acc[k][2];
                     double h1[3], h2[3], h3[3], h4[3];
@@ -405,22 +412,10 @@ __global__ __launch_bounds__(512) void fused_chain_tsqr_kernel(
         return;
     }
     // ======================================================================================================= consumers
-    constexpr int LCH = NCC - 1;  // chunks of the triangle kept in LDS (RLAST form)
     const int c_id = wave - G::NPROD;
     const int pad = 16 * NCC - nc;
-    int skip = 0;
-    for (int kp = 0; kp < pad; ++kp) skip += 16 * (LCH - (kp >> 4) > 0 ? LCH - (kp >> 4) : 0);
-    double *mine = lds + G::CONS0 + c_id * tri_doubles;
-    Tsqr2State<NCC, NRC, true> S;
-    S.red = mine;
-    S.bc = mine + 64;
-    S.Rl = mine + 80 - skip;
-    S.lane_c = lane & 15;
-    S.lane_g = lane >> 4;
-    S.nc = nc;
-    S.null2 = null2;
-#pragma unroll
-    for (int sl = 0; sl < 4 * NCC; ++sl) S.Rq[sl] = 0.0;
+    Tsqr2State<NCC, NRC, true> S;  // (RLAST form: the last chunk of the triangle in registers)
+    tsqr2_state_init(S, lds + G::CONS0 + c_id * tri_doubles, lane, nc, null2);
     // per-lane column sources inside an LDS tile: kept column col_idx[col] for col < n, the tau slot (column NC) for
     // col == n == nc - 1; padding lane-columns stay exactly zero for the whole kernel
     bool wlive[NCC];
@@ -432,10 +427,6 @@ __global__ __launch_bounds__(512) void fused_chain_tsqr_kernel(
         const int src = (col >= 0 && col < n) ? col_idx[col] : NC;
         loff[cc] = S.lane_g * LDT + src;
     }
-#pragma unroll
-    for (int cc = 0; cc < NCC; ++cc)
-#pragma unroll
-        for (int i = 0; i < RPL; ++i) S.T[cc][i] = 0.0;
     // structure of the joint-torque regressor of a chain (regressor.py:45-87): the row block of joint j has exact zeros in the
     // columns of the links in front of j -- the producer writes them as such -- so a tile's first kept column that can be
     // non-zero is known from its row block: fpos[j] = pad + #{kept columns < 14 j}.  Chunks in front of it are not gathered.
@@ -488,9 +479,7 @@ __global__ __launch_bounds__(512) void fused_chain_tsqr_kernel(
         asm volatile("" ::: "memory");
         const double *tile = lds + pick * G::PSIZE;
         FusedCtrl *ctrl = pick ? ctrl1 : ctrl0;
-        // row block of the tile: the producer's row order 0, NJ-1, 1, NJ-2, ...
-        const int jo = tpick % NJ;
-        const int jrow = (jo & 1) ? NJ - 1 - (jo >> 1) : (jo >> 1);
+        const int jrow = fused_row_of<NJ>(tpick % NJ);  // row block of the tile
         int first_nz = fpos[0];
 #pragma unroll
         for (int j = 1; j < NJ; ++j) first_nz = jrow == j ? fpos[j] : first_nz;
@@ -512,90 +501,61 @@ __global__ __launch_bounds__(512) void fused_chain_tsqr_kernel(
 #pragma unroll
             for (int i = 0; i < RPL; ++i) asm volatile("" : "+v"(S.T[cc][i]));
         lds_post(&ctrl->taken, tpick + 1);
-        S.null2 = absorbed * 64 < nc + 8 ? 0.0 : null2;  // (null pivots once the triangle is of full height: see tsqr2_level0_body)
+        S.null2 = tsqr2_null2_at(absorbed, 64, nc, null2);
         ++absorbed;
         tsqr2_panels<0, NCC, NRC, false, true>(S, first_nz, [](auto) {});
     }
-    // this wave's triangle (compact nc x nc, row-major): the LDS chunks, then the register chunk
-    double *Rg = Rws + (wg * ncons + c_id) * (long)nc * nc;
-    const int nlds = 16 * LCH - pad;  // columns of the compact triangle that live in LDS
-    for (int e = lane; e < nc * nc; e += 64) {
-        const int k = e / nc, col = e - k * nc;
-        if (col >= nlds && col >= k) continue;  // (written from the registers below)
-        const int kp = k + pad, colp = col + pad;
-        const int pk = kp >> 4;
-        Rg[e] = (col < k) ? 0.0 : S.Rl[tsqr2_panel_off<LCH>(pk) + (kp & 15) * 16 * (LCH - pk) + (colp - 16 * pk)];
-    }
-    {
-        const int col = 16 * LCH + S.lane_c - pad;
-#pragma unroll
-        for (int sl = 0; sl < 4 * NCC; ++sl) {
-            const int k = 4 * sl + S.lane_g - pad;
-            if (k >= 0 && col >= k && col >= 0) Rg[(long)k * nc + col] = S.Rq[sl];
-        }
-    }
-}
-
-// partial[b][c] -> out[c]: one workgroup per column, strided partial sums + LDS tree (fixed order: deterministic)
-__global__ __launch_bounds__(256) void fused_reduce_partials_kernel(const double *__restrict__ part, int nblocks, int ncols,
-                                                                    double *__restrict__ out) {
-    __shared__ double sm[256];
-    const int c = blockIdx.x;
-    double s = 0.0;
-    for (int b = threadIdx.x; b < nblocks; b += 256) s += part[(long)b * ncols + c];
-    sm[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) sm[threadIdx.x] += sm[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[c] = sm[0];
+    tsqr2_store_triangle(S, Rws + (wg * ncons + c_id) * (long)nc * nc, nc, pad, lane);
 }
 
 // One merge level of the batched form: workgroup (bl, b) factors the stacked rows [512 bl, 512 (bl + 1)) of trajectory b's
 // input -- `rows` rows of its own triangles (Rs + b * rows * nc), then, when `extra` is given, the nc rows of that
-// triangle, the same for every trajectory -- into triangle bl of the trajectory's gridDim.x outputs.  tsqr_coop_kernel<4, 8>
-// (figh_linalg.hip) with a trajectory index; the zero fill leaves exact zeros below the diagonal.
+// triangle, the same for every trajectory -- into triangle bl of the trajectory's gridDim.x outputs: tsqr_coop_factor<4, 8>
+// over the two sources; the zero fill leaves exact zeros below the diagonal.
 __global__ __launch_bounds__(512) void fused_batch_merge_kernel(const double *__restrict__ Rs, const long rows,
                                                                 const double *__restrict__ extra, const int nc,
                                                                 double *__restrict__ Rout) {
-    constexpr int NCC = 4, NW = 8;
-    __shared__ double pw[2][NW][16 * NCC];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int lane_c = lane & 15, lane_g = lane >> 4;
-    const long r0 = ((long)blockIdx.x * NW + wave) * 64;
-    const int pad = 16 * NCC - nc;
     const double *mine = Rs + (long)blockIdx.y * rows * nc;
     const long rows_all = rows + (extra ? nc : 0);
     double *Rg = Rout + ((long)blockIdx.y * gridDim.x + blockIdx.x) * nc * nc;
-    for (int e = threadIdx.x; e < nc * nc; e += 64 * NW) Rg[e] = 0.0;
-    double T[NCC][16];
-#pragma unroll
-    for (int cc = 0; cc < NCC; ++cc)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const long row = r0 + 16 * (i >> 2) + lane_g + 4 * (i & 3);
-            const int col = 16 * cc + lane_c - pad;
-            const bool ok = row < rows_all && col >= 0;
-            const double *src = row < rows ? mine + row * nc : extra + (row - rows) * nc;
-            const double v = ok ? src[col] : 0.0;
-            T[cc][i] = v;
-        }
-    __syncthreads();  // the zero fill of Rg is ordered before the row stores of wave 0 (same workgroup)
-    tsqr_coop_panels<0, NCC, NW>(T, nc, pad, lane_c, lane_g, wave, pw, Rg);
+    tsqr_coop_factor<4, 8>((long)blockIdx.x, nc, Rg, [&](const long row, const int col) {
+        const bool ok = row < rows_all && col >= 0;
+        const double *src = row < rows ? mine + row * nc : extra + (row - rows) * nc;
+        return ok ? src[col] : 0.0;
+    });
 }
 
-static size_t fused_tri_doubles(int nc) {  // LDS per consumer: 64 + 16 doubles of scratch + the three LDS chunks of the triangle
-    const int pad = 64 - nc;
-    size_t skip = 0;
-    for (int kp = 0; kp < pad; ++kp) skip += 16 * (3 - (kp >> 4) > 0 ? 3 - (kp >> 4) : 0);
-    return 80 + 256 * (size_t)(3 + 2 + 1) - skip;
-}
+// What both launchers need of the level-0 kernel: the chain constants, the LDS doubles per consumer (the RLAST triangle of
+// four chunks, tsqr2_tri_doubles), the consumer waves per workgroup -- what fits behind the producers' doubles in 160 KB
+// of LDS, at most six -- and the dynamic LDS of the launch, which the kernel is allowed once per instantiation.
+template <int NJ>
+struct FusedPlan {
+    ChainParams<NJ> P;
+    int tri, ncons;
+    size_t lds;
+};
 
-// consumer waves per workgroup: what fits behind the `fixed` doubles of the producers in 160 KB of LDS, at most six
-static int fused_consumers(size_t fixed, size_t tri) {
-    const size_t budget = (160 * 1024) / sizeof(double);
-    return (int)std::min<size_t>(6, (budget - fixed) / tri);
+template <int NJ, bool TRAJ>
+static int fused_plan(const figh_model_s *m, int nc, FusedPlan<NJ> *plan) {
+    constexpr size_t fixed = FusedGeom<NJ>::CONS0, budget = (160 * 1024) / sizeof(double);
+    const size_t tri = (size_t)tsqr2_tri_doubles(4, nc, true);
+    const int ncons = (int)std::min<size_t>(6, (budget - fixed) / tri);
+    if (ncons < 3) {
+        set_error(std::string(TRAJ ? "fused batch regressor + TSQR" : "fused regressor + TSQR") +
+                  ": the triangles of three consumer waves do not fit next to the tile");
+        return FIGH_ERR_UNSUPPORTED;
+    }
+    static bool attr_set = false;
+    if (!attr_set) {
+        FIGH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fused_chain_tsqr_kernel<NJ, TRAJ>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        attr_set = true;
+    }
+    plan->P = chain_params<NJ>(m);
+    plan->tri = (int)tri;
+    plan->ncons = ncons;
+    plan->lds = sizeof(double) * (fixed + (size_t)ncons * tri);
+    return FIGH_OK;
 }
 
 template <int NJ>
@@ -604,36 +564,20 @@ static int launch_fused(const figh_model_s *m, int flags, long N, const double *
                         long *count_out) {
     using G = FusedGeom<NJ>;
     const int nc = n + (tau ? 1 : 0);
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const size_t tri = fused_tri_doubles(nc);
-    const size_t fixed = (size_t)G::CONS0;
-    const int ncons = fused_consumers(fixed, tri);
-    if (ncons < 3) {
-        set_error("fused regressor + TSQR: the triangles of three consumer waves do not fit next to the tile");
-        return FIGH_ERR_UNSUPPORTED;
-    }
+    FusedPlan<NJ> pl;
+    if (int rc = fused_plan<NJ, false>(m, nc, &pl)) return rc;
+    const int cus = cu_count(), ncons = pl.ncons;
     const long ntiles_s = (N + 63) / 64;
     long grid = cus < ntiles_s / 2 ? cus : ntiles_s / 2;  // (at least two sample tiles = 12 row tiles per workgroup)
-    const size_t lds = sizeof(double) * (fixed + (size_t)ncons * tri);
-    static bool attr_set[16] = {};
-    if (!attr_set[NJ]) {
-        FIGH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fused_chain_tsqr_kernel<NJ>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set[NJ] = true;
-    }
     double *part = static_cast<double *>(workspace(sizeof(double) * grid * G::NPROD * G::NC, kWsRegressorNorms));
     double *Rws = static_cast<double *>(workspace(sizeof(double) * (size_t)nc * nc * (grid * ncons + 1), kWsLevel0TriOrWrench));
     if (!part || !Rws) return FIGH_ERR_ALLOC;
-    const ChainParams<NJ> P = chain_params<NJ>(m);
     {
         ProfileScope scope("fused_chain_tsqr", true);
-        FIGH_LAUNCH_TIMED((fused_chain_tsqr_kernel<NJ>), dim3((unsigned)grid), dim3(64 * (G::NPROD + ncons)), lds, P, flags, N, q,
-                          v, a, W, tau, d_kept, n, nc, part, Rws, ncons, (int)tri, null_pivot_sq());
+        FIGH_LAUNCH_TIMED((fused_chain_tsqr_kernel<NJ, false>), dim3((unsigned)grid), dim3(64 * (G::NPROD + ncons)), pl.lds,
+                          pl.P, flags, N, q, v, a, W, tau, d_kept, n, nc, part, Rws, ncons, pl.tri, null_pivot_sq());
     }
-    hipLaunchKernelGGL(fused_reduce_partials_kernel, dim3(G::NC), dim3(256), 0, stream(), part, (int)(grid * G::NPROD),
-                       G::NC, d_colsq);
+    launch_reduce_partials(part, (int)(grid * G::NPROD), G::NC, d_colsq);
     FIGH_HIP(hipGetLastError());
     *Rws_out = Rws;
     *count_out = grid * ncons;
@@ -654,33 +598,18 @@ static int launch_fused_batch(const figh_model_s *m, int flags, long B, long n_p
                               const double *a, const int *d_cols, int n, const double *d_R_stack, double *d_R_out) {
     using G = FusedGeom<NJ>;
     const int nc = n;
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const size_t tri = fused_tri_doubles(nc);
-    const size_t fixed = (size_t)G::CONS0;
-    const int ncons = fused_consumers(fixed, tri);
-    if (ncons < 3) {
-        set_error("fused batch regressor + TSQR: the triangles of three consumer waves do not fit next to the tile");
-        return FIGH_ERR_UNSUPPORTED;
-    }
-    const long S = fused_batch_slices(B, n_per, cus);
-    const size_t lds = sizeof(double) * (fixed + (size_t)ncons * tri);
-    static bool attr_set[16] = {};
-    if (!attr_set[NJ]) {
-        FIGH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fused_chain_tsqr_kernel<NJ, true>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set[NJ] = true;
-    }
+    FusedPlan<NJ> pl;
+    if (int rc = fused_plan<NJ, true>(m, nc, &pl)) return rc;
+    const int ncons = pl.ncons;
+    const long S = fused_batch_slices(B, n_per, cu_count());
     const size_t tsz = sizeof(double) * (size_t)nc * nc;
     double *Rws = static_cast<double *>(workspace(tsz * (size_t)(B * S * ncons), kWsFusedBatchTri));
     if (!Rws) return FIGH_ERR_ALLOC;
-    const ChainParams<NJ> P = chain_params<NJ>(m);
     {
         ProfileScope scope("fused_chain_tsqr_batch", true);
         FIGH_LAUNCH_TIMED((fused_chain_tsqr_kernel<NJ, true>), dim3((unsigned)S, (unsigned)B), dim3(64 * (G::NPROD + ncons)),
-                          lds, P, flags, n_per, q, v, a, (double *)nullptr, (const double *)nullptr, d_cols, n, nc,
-                          (double *)nullptr, Rws, ncons, (int)tri, null_pivot_sq());
+                          pl.lds, pl.P, flags, n_per, q, v, a, (double *)nullptr, (const double *)nullptr, d_cols, n, nc,
+                          (double *)nullptr, Rws, ncons, pl.tri, null_pivot_sq());
     }
     FIGH_HIP(hipGetLastError());
     // merge levels: cnt triangles per trajectory (+ d_R_stack at the first level) -> ceil(rows / 512) -> ... -> 1
@@ -729,14 +658,15 @@ extern "C" int figh_regressor_tsqr_fused(figh_model_t model, int flags, int64_t 
     int rc;
     const int f = flags & 7;
     switch (h.nlinks) {
-#define FIGH_FUSED_CASE(NJ)                                                                                       \
-    case NJ:                                                                                                      \
-        rc = launch_fused<NJ>(model, f, (long)N, d_q, d_v, d_a, d_W, d_tau, d_kept, n, d_colsq, &Rws, &count);    \
-        break;
-        FIGH_FUSED_CASE(5)
-        FIGH_FUSED_CASE(6)
-        FIGH_FUSED_CASE(7)
-#undef FIGH_FUSED_CASE
+        case 5:
+            rc = launch_fused<5>(model, f, (long)N, d_q, d_v, d_a, d_W, d_tau, d_kept, n, d_colsq, &Rws, &count);
+            break;
+        case 6:
+            rc = launch_fused<6>(model, f, (long)N, d_q, d_v, d_a, d_W, d_tau, d_kept, n, d_colsq, &Rws, &count);
+            break;
+        case 7:
+            rc = launch_fused<7>(model, f, (long)N, d_q, d_v, d_a, d_W, d_tau, d_kept, n, d_colsq, &Rws, &count);
+            break;
         default:
             // (eight links: two 58 KB tile buffers leave 17 KB of the 160 KB of LDS, less than three consumer triangles)
             set_error("fused regressor + TSQR: serial chains of 5 to 7 joints (LDS: two tile buffers + three consumer triangles)");
@@ -786,7 +716,9 @@ extern "C" int figh_regressor_tsqr_batch_fused(figh_model_t model, int flags, in
             return launch_fused_batch<5>(model, f, (long)B, (long)n_per, d_q, d_v, d_a, d_col_idx, n, d_R_stack, d_R_out);
         case 6:
             return launch_fused_batch<6>(model, f, (long)B, (long)n_per, d_q, d_v, d_a, d_col_idx, n, d_R_stack, d_R_out);
-        default:
+        case 7:
             return launch_fused_batch<7>(model, f, (long)B, (long)n_per, d_q, d_v, d_a, d_col_idx, n, d_R_stack, d_R_out);
+        default:  // (refused above)
+            return FIGH_ERR_UNSUPPORTED;
     }
 }

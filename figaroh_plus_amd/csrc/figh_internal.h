@@ -47,6 +47,7 @@ void set_error(const std::string &msg);
 double null_pivot_sq();  // square of figh_tsqr_null_pivot_tol (0: exact zeros only)
 hipStream_t stream();
 int ensure_device();
+int cu_count();  // compute units of the device that is current at the first call (256 when the query fails); asked once
 
 // per-kernel-family hipEvent timing (figh_profile_*).  Two forms:
 //   ProfileScope s("name")           events recorded on the stream around everything launched inside the scope;
@@ -152,6 +153,10 @@ int64_t tsqr_level0_capacity(int nc);
 // the device per-tile hint of row blocks that are zero in front of column h_first_col[b] (nullptr in *out for more than 80
 // columns: only the register-tile kernel reads it)
 int tile_hint(const int32_t *h_first_col, int nfirst, int64_t rows, int n, int nc, const int **out);
+
+// figh_linalg.hip: part[b][c], b < nblocks -> out[c] = sum over b, in a fixed order (the diag(W^T W) partials of figh_colsq,
+// the chain regressor and the fused chain TSQR); queued on stream(), the caller checks hipGetLastError
+void launch_reduce_partials(const double *part, int nblocks, int ncols, double *out);
 
 // figh_regressor_tree.hip: K1' for kinematic trees (tape-driven); *colsq_done = 1 when diag(W^T W) was fused
 int launch_regressor_tree(const figh_model_s *m, int mode, int flags, int ft_mask, long N, const double *q,

@@ -45,26 +45,7 @@ __global__ __launch_bounds__(64, (NCC <= 4 || RLAST) ? 2 : 1) void tsqr2_kernel(
 template <int NCC, int NW>
 __global__ __launch_bounds__(64 * NW) void tsqr_coop_kernel(const double *__restrict__ Rs, const long rows, const int nc,
                                                             double *__restrict__ Rout) {
-    __shared__ double pw[2][NW][16 * NCC];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int lane_c = lane & 15, lane_g = lane >> 4;
-    const long r0 = ((long)blockIdx.x * NW + wave) * 64;
-    const int pad = 16 * NCC - nc;  // columns right-aligned, as in tsqr2_kernel
-    double *Rg = Rout + (long)blockIdx.x * nc * nc;
-    for (int e = threadIdx.x; e < nc * nc; e += 64 * NW) Rg[e] = 0.0;
-    double T[NCC][16];
-#pragma unroll
-    for (int cc = 0; cc < NCC; ++cc)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const long row = r0 + 16 * (i >> 2) + lane_g + 4 * (i & 3);
-            const int col = 16 * cc + lane_c - pad;
-            const bool ok = row < rows && col >= 0;
-            const double v = Rs[(ok ? row : 0) * nc + (ok ? col : 0)];
-            T[cc][i] = ok ? v : 0.0;
-        }
-    __syncthreads();  // the zero fill of Rg is ordered before the row stores of wave 0 (same workgroup)
-    tsqr_coop_panels<0, NCC, NW>(T, nc, pad, lane_c, lane_g, wave, pw, Rg);
+    tsqr_coop_factor<NCC, NW>((long)blockIdx.x, nc, Rout + (long)blockIdx.x * nc * nc, CoopStackRows{Rs, rows, nc});
 }
 
 
@@ -90,8 +71,9 @@ __global__ __launch_bounds__(256) void colsq_kernel(const double *__restrict__ W
     }
 }
 
-__global__ __launch_bounds__(256) void reduce_cols_kernel(const double *__restrict__ part, int nblocks, int ncols,
-                                                          double *__restrict__ out) {
+// partial[b][c] -> out[c]: one workgroup per column, strided partial sums + LDS tree (fixed order: deterministic)
+__global__ __launch_bounds__(256) void reduce_partials_kernel(const double *__restrict__ part, int nblocks, int ncols,
+                                                              double *__restrict__ out) {
     __shared__ double sm[256];
     const int c = blockIdx.x;
     double s = 0.0;
@@ -103,6 +85,10 @@ __global__ __launch_bounds__(256) void reduce_cols_kernel(const double *__restri
         __syncthreads();
     }
     if (threadIdx.x == 0) out[c] = sm[0];
+}
+
+void launch_reduce_partials(const double *part, int nblocks, int ncols, double *out) {
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3(ncols), dim3(256), 0, stream(), part, nblocks, ncols, out);
 }
 
 __global__ __launch_bounds__(256) void gather_cols_kernel(const double *__restrict__ W, long rows, long ldw,
@@ -402,24 +388,8 @@ __global__ __launch_bounds__(256) void compact_copy_kernel(const double *__restr
     }
 }
 
-static int cu_count() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    }
-    return cus;
-}
-
-
 // LDS of one tsqr2 wave: 64 doubles of reduction scratch + the packed triangle minus the rows of the padding columns
-static size_t tsqr2_lds_bytes(int ncc, int nc, bool rlast = false) {
-    const int pad = 16 * ncc - nc, lch = rlast ? ncc - 1 : ncc;
-    size_t skip = 0;
-    for (int kp = 0; kp < pad; ++kp) skip += 16 * (lch - (kp >> 4) > 0 ? lch - (kp >> 4) : 0);
-    return sizeof(double) * ((rlast ? 80 : 64) + 256 * (size_t)(lch * lch - (lch * (lch - 1)) / 2) - skip);
-}
+static size_t tsqr2_lds_bytes(int ncc, int nc, bool rlast = false) { return sizeof(double) * tsqr2_tri_doubles(ncc, nc, rlast); }
 
 __global__ __launch_bounds__(256) void tile_hint_kernel(const int *__restrict__ first, const long hint_rows,
                                                         const long rows, const long ntiles, int *__restrict__ out) {
@@ -570,8 +540,7 @@ int figh_colsq(const double *d_W, int64_t rows, int cols, int64_t ldw, double *d
     ProfileScope scope("colsq");
     hipLaunchKernelGGL(colsq_kernel, dim3((unsigned)nblocks), dim3(256), 0, stream(), d_W, (long)rows, cols, (long)ldw,
                        rpb, part);
-    hipLaunchKernelGGL(reduce_cols_kernel, dim3(cols), dim3(256), 0, stream(), part, (int)nblocks, cols,
-                       d_out);
+    launch_reduce_partials(part, (int)nblocks, cols, d_out);
     FIGH_HIP(hipGetLastError());
     return FIGH_OK;
 }

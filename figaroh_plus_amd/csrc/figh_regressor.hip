@@ -150,27 +150,7 @@ __global__ __launch_bounds__(64) void regressor_chain_kernel(const ChainParams<N
                     }
                 }
                 double *o = my + 14 * k;
-                // m
-                o[9] = Jl[0] * acc[k][0] + Jl[1] * acc[k][1] + Jl[2] * acc[k][2];
-                // mx my mz : Jl x dw + w x (w x Jl) + acc x Ja
-                double h1[3], h2[3], h3[3], h4[3];
-                cross3(Jl, dw[k], h1);
-                cross3(w[k], Jl, h2);
-                cross3(w[k], h2, h3);
-                cross3(acc[k], Ja, h4);
-                o[6] = h1[0] + h3[0] + h4[0];
-                o[7] = h1[1] + h3[1] + h4[1];
-                o[8] = h1[2] + h3[2] + h4[2];
-                // inertia: L(dw)^T Ja - L(w)^T (w x Ja),  L(x)^T y = [x0y0, x1y0+x0y1, x1y1, x2y0+x0y2, x2y1+x1y2, x2y2]
-                double u[3];
-                cross3(w[k], Ja, u);
-                const double *x = dw[k], *z = w[k];
-                o[0] = x[0] * Ja[0] - z[0] * u[0];                                        // Ixx
-                o[1] = x[1] * Ja[0] + x[0] * Ja[1] - (z[1] * u[0] + z[0] * u[1]);          // Ixy
-                o[3] = x[1] * Ja[1] - z[1] * u[1];                                        // Iyy
-                o[2] = x[2] * Ja[0] + x[0] * Ja[2] - (z[2] * u[0] + z[0] * u[2]);          // Ixz
-                o[4] = x[2] * Ja[1] + x[1] * Ja[2] - (z[2] * u[1] + z[1] * u[2]);          // Iyz
-                o[5] = x[2] * Ja[2] - z[2] * u[2];                                        // Izz
+                axis_times_body_regressor(Jl, Ja, acc[k], dw[k], w[k], o);  // Ixx .. Izz mx my mz m
                 // Ia fv fs off: only on the link's own row (regressor.py:55-70,84-87)
                 const bool own = (k == j);
                 o[10] = (own && actin) ? qdd[k] : 0.0;
@@ -315,22 +295,6 @@ __global__ __launch_bounds__(64) void regressor_chain_kernel(const ChainParams<N
     }
 }
 
-// partial[b][c] -> out[c]: one workgroup per column, strided partial sums + LDS tree (fixed order: deterministic)
-__global__ __launch_bounds__(256) void reduce_partials_kernel(const double *__restrict__ part, int nblocks, int ncols,
-                                                              double *__restrict__ out) {
-    __shared__ double sm[256];
-    const int c = blockIdx.x;
-    double s = 0.0;
-    for (int b = threadIdx.x; b < nblocks; b += 256) s += part[(long)b * ncols + c];
-    sm[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) sm[threadIdx.x] += sm[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[c] = sm[0];
-}
-
 __global__ __launch_bounds__(256) void coupling_tx40_kernel(const long N, const int nv, const double *__restrict__ v,
                                                             const double *__restrict__ a, double *__restrict__ out) {
     for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < 6 * N; e += (long)gridDim.x * blockDim.x) {
@@ -353,18 +317,9 @@ template <int NJ, bool TX40>
 static int launch_chain(const figh_model_s *m, int flags, long N, const double *q, const double *v, const double *a,
                         double *W, long ldw, double *d_colsq) {
     using G = ChainGeom<NJ, TX40>;
-    ChainParams<NJ> P;
-    const DevModel &h = m->host;
-    for (int k = 0; k < NJ; ++k) {
-        for (int d = 0; d < 3; ++d) P.axis[k][d] = h.axis[k + 1][d];
-        for (int d = 0; d < 9; ++d) P.Rp[k][d] = h.placement[k + 1][d];
-        for (int d = 0; d < 3; ++d) P.pp[k][d] = h.placement[k + 1][9 + d];
-    }
-    for (int d = 0; d < 3; ++d) P.g[d] = h.gravity[d];
+    const ChainParams<NJ> P = chain_params<NJ>(m);
     const long ntiles = (N + 63) / 64;
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int cus = cu_count();
     const size_t lds = sizeof(double) * 64 * G::LDT;
     const int per_cu = (int)((160 * 1024) / lds);
     long grid = (long)cus * (per_cu > 0 ? per_cu : 1) * 2;
@@ -377,8 +332,7 @@ static int launch_chain(const figh_model_s *m, int flags, long N, const double *
         if (!part) return FIGH_ERR_ALLOC;
         FIGH_LAUNCH_TIMED((regressor_chain_kernel<NJ, TX40, true>), dim3((unsigned)grid), dim3(64), lds, P, flags, N, q, v, a,
                           W, ldw, vec_ok, part);
-        hipLaunchKernelGGL(reduce_partials_kernel, dim3(G::NC), dim3(256), 0, stream(), part, (int)grid,
-                           G::NC, d_colsq);
+        launch_reduce_partials(part, (int)grid, G::NC, d_colsq);
     } else {
         FIGH_LAUNCH_TIMED((regressor_chain_kernel<NJ, TX40, false>), dim3((unsigned)grid), dim3(64), lds, P, flags, N, q, v,
                           a, W, ldw, vec_ok, (double *)nullptr);

@@ -46,37 +46,17 @@ __global__ __launch_bounds__(64, 2) void tsqr2_group_kernel(const Tsqr2Job *__re
 }
 
 // ------------------------------------------------------------------------------------------------ merge levels
-// tsqr_coop_kernel<4, 8> per job: workgroup b of the job factors the stacked rows [512 b, 512 (b + 1)) of the level's input
+// tsqr_coop_factor<4, 8> per job: workgroup b of the job factors the stacked rows [512 b, 512 (b + 1)) of the level's input
 // (level 0's triangles, then the previous level's).
 __global__ __launch_bounds__(512) void tsqr_coop_group_kernel(const Tsqr2Job *__restrict__ jobs,
                                                               const int *__restrict__ job_of_wg, const int level) {
-    constexpr int NCC = 4, NW = 8;
-    __shared__ double pw[2][NW][16 * NCC];
     const int jid = __builtin_amdgcn_readfirstlane(job_of_wg[blockIdx.x]);
     const Tsqr2Job *J = jobs + jid;  // (read in place: a local copy with its level-indexed arrays would live in scratch)
     const int nc = J->nc;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int lane_c = lane & 15, lane_g = lane >> 4;
     const int bl = (int)blockIdx.x - J->wg0[level];
     const double *Rs = level == 0 ? J->tri : J->lvl[level - 1];
     const long rows = (long)(level == 0 ? J->nwaves : J->nb[level - 1]) * nc;
-    double *Rg = J->lvl[level] + (long)bl * nc * nc;
-    const long r0 = ((long)bl * NW + wave) * 64;
-    const int pad = 16 * NCC - nc;
-    for (int e = threadIdx.x; e < nc * nc; e += 64 * NW) Rg[e] = 0.0;
-    double T[NCC][16];
-#pragma unroll
-    for (int cc = 0; cc < NCC; ++cc)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const long row = r0 + 16 * (i >> 2) + lane_g + 4 * (i & 3);
-            const int col = 16 * cc + lane_c - pad;
-            const bool ok = row < rows && col >= 0;
-            const double v = Rs[(ok ? row : 0) * nc + (ok ? col : 0)];
-            T[cc][i] = ok ? v : 0.0;
-        }
-    __syncthreads();
-    tsqr_coop_panels<0, NCC, NW>(T, nc, pad, lane_c, lane_g, wave, pw, Rg);
+    tsqr_coop_factor<4, 8>((long)bl, nc, J->lvl[level] + (long)bl * nc * nc, CoopStackRows{Rs, rows, nc});
 }
 
 // ------------------------------------------------------------------------------------------------ embedding
@@ -181,10 +161,7 @@ int launch_tsqr_group(std::vector<Tsqr2Job> &jobs, int ncfull, int nfull, int cu
     const Tsqr2Job *d_jobs = reinterpret_cast<const Tsqr2Job *>(dev);
     const int *d_maps = reinterpret_cast<const int *>(dev + jb);
     // LDS of one level-0 wave: the packed triangle of the widest job (64 doubles of scratch in front)
-    const int padm = 64 - max_nc;
-    size_t skipm = 0;
-    for (int kp = 0; kp < padm; ++kp) skipm += 16 * (4 - (kp >> 4));
-    const size_t lds = sizeof(double) * (64 + 256 * 10 - skipm);
+    const size_t lds = sizeof(double) * tsqr2_tri_doubles(4, max_nc, false);
 
     long max_tiles = 1;
     for (auto &J : jobs) max_tiles = std::max(max_tiles, (J.rows + 63) / 64);  // (enough for either tile height)

@@ -1,5 +1,6 @@
-// Column steps of the register-tile TSQR (n <= 16*NCC <= 80 columns), shared by tsqr2_kernel (figh_linalg.hip) and the
-// fused regressor + TSQR kernel (figh_fused.hip).
+// The register-tile TSQR (n <= 16*NCC <= 80 columns): the wave's state, its LDS size (host and device), the column steps and
+// the triangle write-back shared by tsqr2_kernel (figh_linalg.hip), the grouped launch (figh_tsqr_group.hip) and the fused
+// regressor + TSQR kernel (figh_fused.hip); the cooperative sweep of the merge levels (tsqr_coop_factor) for all three files.
 #pragma once
 
 #include <type_traits>
@@ -38,6 +39,75 @@ struct Tsqr2State {
 // doubles of LDS in front of row 0 of panel P in the packed triangle (LCH chunks per row of panel 0)
 template <int LCH>
 constexpr int tsqr2_panel_off(int P) { return 256 * (P * LCH - (P * (P - 1)) / 2); }
+
+// The packed triangle leaves out the rows of the `pad` padding columns in front: so many doubles (lch chunks in LDS)
+__host__ __device__ constexpr int tsqr2_tri_skip(int pad, int lch) {
+    int skip = 0;
+    for (int kp = 0; kp < pad; ++kp) skip += 16 * (lch - (kp >> 4) > 0 ? lch - (kp >> 4) : 0);
+    return skip;
+}
+
+// LDS doubles of one wave: 64 of reduction scratch (+ 16 for a row of the register chunk, RLAST), then the packed triangle
+__host__ __device__ constexpr int tsqr2_tri_doubles(int ncc, int nc, bool rlast) {
+    const int lch = rlast ? ncc - 1 : ncc;
+    return (rlast ? 80 : 64) + 256 * (lch * lch - (lch * (lch - 1)) / 2) - tsqr2_tri_skip(16 * ncc - nc, lch);
+}
+
+// The wave's state over its tsqr2_tri_doubles of LDS at lds_base, tile and register chunk zeroed.  Zeroing the LDS is the
+// caller's: a wave-private loop in the two-launch kernel, the whole workgroup's in the fused one.
+template <int NCC, int NRC, bool RLAST>
+__device__ __forceinline__ void tsqr2_state_init(Tsqr2State<NCC, NRC, RLAST> &S, double *lds_base, const int lane,
+                                                 const int nc, const double null2) {
+    constexpr int LCH = RLAST ? NCC - 1 : NCC;
+    S.red = lds_base;
+    S.bc = lds_base + 64;
+    S.Rl = lds_base + (RLAST ? 80 : 64) - tsqr2_tri_skip(16 * NCC - nc, LCH);
+    S.lane_c = lane & 15;
+    S.lane_g = lane >> 4;
+    S.nc = nc;
+    S.null2 = null2;
+    if constexpr (RLAST) {
+#pragma unroll
+        for (int sl = 0; sl < 4 * NCC; ++sl) S.Rq[sl] = 0.0;
+    }
+#pragma unroll
+    for (int cc = 0; cc < NCC; ++cc)
+#pragma unroll
+        for (int i = 0; i < 4 * NRC; ++i) S.T[cc][i] = 0.0;
+}
+
+// Null pivots only once the triangle is of full height: a tile that exhausts the rank of what has been absorbed so far
+// forms its last reflectors from small residuals, which leaves noise of 1e-11 (instead of 1e-13) in the columns behind
+// them -- harmless for a Householder step (the garbage reflectors of the dependent columns annihilate it), but a null
+// pivot would keep it as its |R_kk| (tools/null_pivot_noise.py).  `absorbed` tiles of M rows have been factored.
+__device__ __forceinline__ double tsqr2_null2_at(const int absorbed, const int M, const int nc, const double null2) {
+    return absorbed * M < nc + M / 8 ? 0.0 : null2;
+}
+
+// The wave's triangle, compact nc x nc and row-major, to Rg: the LDS chunks, then (RLAST) the register chunk
+template <int NCC, int NRC, bool RLAST>
+__device__ __forceinline__ void tsqr2_store_triangle(const Tsqr2State<NCC, NRC, RLAST> &S, double *__restrict__ Rg,
+                                                     const int nc, const int pad, const int lane) {
+    constexpr int LCH = RLAST ? NCC - 1 : NCC;
+    const int nlds = 16 * LCH - pad;  // columns of the compact triangle that live in LDS
+    for (int e = lane; e < nc * nc; e += 64) {
+        const int k = e / nc, col = e - k * nc;
+        if (RLAST && col >= nlds && col >= k) continue;  // (written from the registers below)
+        const int kp = k + pad, colp = col + pad;  // padded positions
+        const int pk = kp >> 4;
+        Rg[e] = (k >= nc || col < k)  // below the diagonal the LDS rows hold rounding residues, not results
+                    ? 0.0
+                    : S.Rl[tsqr2_panel_off<LCH>(pk) + (kp & 15) * 16 * (LCH - pk) + (colp - 16 * pk)];
+    }
+    if constexpr (RLAST) {
+        const int col = 16 * LCH + S.lane_c - pad;
+#pragma unroll
+        for (int sl = 0; sl < 4 * NCC; ++sl) {
+            const int k = 4 * sl + S.lane_g - pad;
+            if (k >= 0 && col >= k && col >= 0 && col < nc) Rg[(long)k * nc + col] = S.Rq[sl];
+        }
+    }
+}
 
 // The panel index P is a compile-time constant: the chunk registers T[P .. NCC-1] are addressed statically (no
 // rotation copies), the number of live chunks is known, and a step is straight-line code -- after the pivot chunk's
@@ -262,5 +332,37 @@ __device__ __forceinline__ void tsqr_coop_panels(double (&T)[NCC][16], const int
     if constexpr (P + 1 < NCC) tsqr_coop_panels<P + 1, NCC, NW>(T, nc, pad, lane_c, lane_g, wave, pw, Rg);
 }
 
+
+// One cooperative sweep: the workgroup zero-fills its output triangle Rg, wave w loads the stacked rows
+// [64 (NW blk + w), + 64) right-aligned into its register tile -- entry(row, col) is the stack's entry, or zero beyond its
+// end and for col < 0 (padding) -- and the NW waves factor their 64 NW rows into Rg.
+template <int NCC, int NW, class Entry>
+__device__ __forceinline__ void tsqr_coop_factor(const long blk, const int nc, double *__restrict__ Rg, Entry &&entry) {
+    __shared__ double pw[2][NW][16 * NCC];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane_c = lane & 15, lane_g = lane >> 4;
+    const long r0 = (blk * NW + wave) * 64;
+    const int pad = 16 * NCC - nc;  // columns right-aligned, as in tsqr2_kernel
+    for (int e = threadIdx.x; e < nc * nc; e += 64 * NW) Rg[e] = 0.0;
+    double T[NCC][16];
+#pragma unroll
+    for (int cc = 0; cc < NCC; ++cc)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) T[cc][i] = entry(r0 + 16 * (i >> 2) + lane_g + 4 * (i & 3), 16 * cc + lane_c - pad);
+    __syncthreads();  // the zero fill of Rg is ordered before the row stores of wave 0 (same workgroup)
+    tsqr_coop_panels<0, NCC, NW>(T, nc, pad, lane_c, lane_g, wave, pw, Rg);
+}
+
+// entry source of tsqr_coop_factor: `rows` contiguous rows of nc doubles (clamped index, then masked: no branch)
+struct CoopStackRows {
+    const double *Rs;
+    long rows;
+    int nc;
+    __device__ __forceinline__ double operator()(const long row, const int col) const {
+        const bool ok = row < rows && col >= 0;
+        const double v = Rs[(ok ? row : 0) * nc + (ok ? col : 0)];
+        return ok ? v : 0.0;
+    }
+};
 
 }  // namespace figh

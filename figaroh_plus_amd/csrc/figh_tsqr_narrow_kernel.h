@@ -37,22 +37,8 @@ __device__ __forceinline__ void tsqr2_level0_body(
     // RLAST (figh_tsqr_narrow.h): the last 16 lane-columns of the triangle live in registers, 16 doubles of LDS pass a row of
     // them between the row groups, and the packed triangle has LCH = NCC - 1 chunks per row -- for 65 .. 80 columns 17 instead
     // of 28 KB per wave, i.e. two waves per SIMD instead of five per CU
-    constexpr int LCH = RLAST ? NCC - 1 : NCC;
-    constexpr int HEAD = RLAST ? 80 : 64;
-    int skip = 0;
-    for (int kp = 0; kp < pad; ++kp) skip += 16 * (LCH - (kp >> 4) > 0 ? LCH - (kp >> 4) : 0);
     Tsqr2State<NCC, NRC, RLAST> S;
-    S.red = Rl;
-    S.bc = Rl + 64;
-    S.Rl = Rl + HEAD - skip;
-    if constexpr (RLAST) {
-#pragma unroll
-        for (int sl = 0; sl < 4 * NCC; ++sl) S.Rq[sl] = 0.0;
-    }
-    S.lane_c = lane & 15;
-    S.lane_g = lane >> 4;
-    S.nc = nc;
-    S.null2 = null2;
+    tsqr2_state_init(S, Rl, lane, nc, null2);
     // per-lane column sources: W[:, col_idx[col]] for col < n; tau is column n = nc - 1, i.e. lane-column 15 of the
     // last chunk; everything else (padding) is a dead lane-column whose registers stay exactly zero for the whole
     // kernel (zero data, zero R row entry => w_j = c_j = 0 in every step), so they are zeroed once and never loaded.
@@ -66,14 +52,7 @@ __device__ __forceinline__ void tsqr2_level0_body(
         loff[cc] = (int)(S.lane_g * ldw) + cidx[cc];  // the host side guarantees ldw < 2^24
     }
     const bool tau_lane = tau != nullptr && S.lane_c == 15;
-#pragma unroll
-    for (int cc = 0; cc < NCC; ++cc)
-#pragma unroll
-        for (int i = 0; i < RPL; ++i) S.T[cc][i] = 0.0;
-    {
-        constexpr int tot = 256 * (LCH * LCH - (LCH * (LCH - 1)) / 2);
-        for (int e = lane; e < HEAD + tot - skip; e += 64) Rl[e] = 0.0;
-    }
+    for (int e = lane, end = tsqr2_tri_doubles(NCC, nc, RLAST); e < end; e += 64) Rl[e] = 0.0;
     __syncthreads();
 
     // Tile loads: lane (g, c) takes rows r0 + 16 rc + g + 4 reg of its column.  Full tiles use a wave-uniform row base
@@ -193,11 +172,7 @@ __device__ __forceinline__ void tsqr2_level0_body(
         if (nzlo) first_nz = __ffsll((long long)nzlo) - 1;
         else if (nzhi) first_nz = 64 + __ffs((int)nzhi) - 1;
 
-        // null pivots only once the triangle is of full height: a tile that exhausts the rank of what has been absorbed so
-        // far forms its last reflectors from small residuals, which leaves noise of 1e-11 (instead of 1e-13) in the columns
-        // behind them -- harmless for a Householder step (the garbage reflectors of the dependent columns annihilate it),
-        // but a null pivot would keep it as its |R_kk| (tools/null_pivot_noise.py)
-        S.null2 = absorbed * M < nc + M / 8 ? 0.0 : null2;
+        S.null2 = tsqr2_null2_at(absorbed, M, nc, null2);
         ++absorbed;
         tsqr2_panels<0, NCC, NRC, LDSRED, RLAST>(S, first_nz, [&](auto P) {
             if constexpr (decltype(P)::value < NCC - 1) {
@@ -208,24 +183,7 @@ __device__ __forceinline__ void tsqr2_level0_body(
     }
     __syncthreads();
     double *Rg = Rws + wave * (long)nc * nc;
-    const int nlds = 16 * LCH - pad;  // columns of the compact triangle that live in LDS
-    for (int e = lane; e < nc * nc; e += 64) {
-        const int k = e / nc, col = e - k * nc;
-        if (RLAST && col >= nlds && col >= k) continue;  // (written from the registers below)
-        const int kp = k + pad, colp = col + pad;  // padded positions
-        const int pk = kp >> 4;
-        Rg[e] = (k >= nc || col < k)  // below the diagonal the LDS rows hold rounding residues, not results
-                    ? 0.0
-                    : S.Rl[tsqr2_panel_off<LCH>(pk) + (kp & 15) * 16 * (LCH - pk) + (colp - 16 * pk)];
-    }
-    if constexpr (RLAST) {
-        const int col = 16 * LCH + S.lane_c - pad;
-#pragma unroll
-        for (int sl = 0; sl < 4 * NCC; ++sl) {
-            const int k = 4 * sl + S.lane_g - pad;
-            if (k >= 0 && col >= k && col >= 0 && col < nc) Rg[(long)k * nc + col] = S.Rq[sl];
-        }
-    }
+    tsqr2_store_triangle(S, Rg, nc, pad, lane);
 }
 
 }  // namespace figh
