@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # FIGH_LIB_PATH: another build of the same ABI (same-box A/B of kernel variants); default is the in-tree library
 LIB_PATH = os.environ.get("FIGH_LIB_PATH") or os.path.join(_HERE, "libfigh.so")
 
-ABI_VERSION = 107  # include/figh.h FIGH_ABI_VERSION: load() refuses a library of another ABI
+ABI_VERSION = 108  # include/figh.h FIGH_ABI_VERSION: load() refuses a library of another ABI
 
 FIGH_OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_ALLOC, ERR_UNSUPPORTED, ERR_COMM = -1, -2, -3, -4, -5
@@ -60,6 +60,8 @@ SIGNATURES = {
                                        C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "figh_regressor_build_padded": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "figh_regressor_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
     "figh_repack_samples": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "figh_coupling_tx40": (C.c_int, [C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "figh_colsq": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p]),
@@ -332,6 +334,26 @@ def regressor_build_padded(model, mode, flags, ft_mask, N, d_q, d_v, d_a, d_W, l
     check(load().figh_regressor_build_padded(model.handle, mode, flags, ft_mask, N, d_q.ptr, d_v.ptr, d_a.ptr,
                                              d_W.ptr if d_W is not None else None, ldw,
                                              d_colsq.ptr if d_colsq is not None else None))
+
+
+APPLY_WAVES_PER_CU = 8  # csrc/figh_dynamics.hip kDynWavesPerCu
+
+
+def regressor_apply_waves(N):
+    """Waves (one per workgroup) of a figh_regressor_apply launch over N samples: one per tile of 64 samples, at most
+    APPLY_WAVES_PER_CU per compute unit, each looping over the tiles (the launch rule of csrc/figh_dynamics.hip)."""
+    return max(1, min((int(N) + 63) // 64, APPLY_WAVES_PER_CU * device_info()["cu_count"]))
+
+
+def regressor_apply(model, mode, flags, ft_mask, N, d_q, d_v, d_a, d_phi, d_tau):
+    """d_tau = W(q, v, a) . phi without W (figh_regressor_apply).  Returns False -- nothing launched, d_tau untouched -- when
+    the library does not serve (model, mode, flags); raises on any other error."""
+    rc = load().figh_regressor_apply(model.handle if model is not None else None, mode, flags, ft_mask, N, d_q.ptr, d_v.ptr,
+                                     d_a.ptr, d_phi.ptr, d_tau.ptr)
+    if rc == ERR_UNSUPPORTED:
+        return False
+    check(rc)
+    return True
 
 
 def coupling_tx40(N, nv, d_v, d_a, d_out):

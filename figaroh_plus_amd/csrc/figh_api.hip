@@ -634,4 +634,33 @@ int figh_regressor_shape(figh_model_t model, int mode, int flags, int *rows_per_
     return FIGH_OK;
 }
 
+// (the kernels are in figh_dynamics.hip)
+int figh_regressor_apply(figh_model_t model, int mode, int flags, int ft_mask, int64_t N, const double *d_q,
+                         const double *d_v, const double *d_a, const double *d_phi, double *d_tau_out) {
+    if (int rc = ensure_device()) return rc;  // (first: without a device no model handle exists either)
+    int rps = 0, ncols = 0;
+    if (int rc = figh_regressor_shape(model, mode, flags, &rps, &ncols)) return rc;
+    FIGH_REQUIRE(N >= 0, "N < 0");
+    FIGH_REQUIRE(d_q && d_v && d_a && d_phi && d_tau_out, "NULL device pointer");
+    const DevModel &h = model->host;
+    if (flags & FIGH_FLAG_BLOCKED_INPUTS) {
+        set_error("figh_regressor_apply reads the reference's sample-major q, v, a: no tile-blocked inputs");
+        return FIGH_ERR_UNSUPPORTED;
+    }
+    if (mode == FIGH_MODE_EXT_WRENCH) {
+        FIGH_REQUIRE((ft_mask & ~63) == 0, "Please enter valid parameters");  // regressor.py:140
+        if (flags & (FIGH_FLAG_FRICTION | FIGH_FLAG_ACT_INERTIA))
+            FIGH_REQUIRE(h.nlinks <= h.nv, "external-wrench friction/inertia columns need njoints-1 <= nv");
+        if (h.jtype[1] != FIGH_JT_FREEFLYER) {
+            set_error("figh_regressor_apply: the external-wrench mode needs a free-flyer root joint");
+            return FIGH_ERR_UNSUPPORTED;
+        }
+    }
+    for (int k = mode == FIGH_MODE_EXT_WRENCH ? 2 : 1; k < h.njoints; ++k)
+        FIGH_REQUIRE(h.jtype[k] != FIGH_JT_FREEFLYER, "a free-flyer joint is only supported as the root joint of the "
+                                                      "external-wrench mode");
+    if (N == 0) return FIGH_OK;
+    return launch_inverse_dynamics(model, mode, flags, ft_mask, N, d_q, d_v, d_a, d_phi, d_tau_out);
+}
+
 }  // extern "C"

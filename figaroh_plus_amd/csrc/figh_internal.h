@@ -117,6 +117,7 @@ enum WorkspaceSlot {
     kWsLinkPos,             // regressor_tsqr_impl: the link map of the link-compact layout
     kWsBlocksMidTri,        // figh_tsqr_selected_blocks: level-0 triangles of the mid blocks
     kWsFusedBatchTri,       // figh_regressor_tsqr_batch_fused: the consumers' triangles of every workgroup
+    kWsDynamicsState,       // figh_regressor_apply (tree kernel): per-wave link wrenches and transforms
     kWorkspaceSlots
 };
 
@@ -163,6 +164,9 @@ int launch_regressor_tree(const figh_model_s *m, int mode, int flags, int ft_mas
                           const double *v, const double *a, double *W, long ldw, int ncols, int link_stride,
                           double *d_colsq, int *colsq_done);
 void forget_tapes(const figh_model_s *m);
+// figh_dynamics.hip: tau = W(q, v, a) . phi by recursive Newton-Euler (arguments checked by figh_regressor_apply)
+int launch_inverse_dynamics(const figh_model_s *m, int mode, int flags, int ft_mask, long N, const double *q, const double *v,
+                            const double *a, const double *phi, double *tau);
 // link -> segment position of the link-compact layout (FIGH_FLAG_LINK_COMPACT), -1 = no segment; returns the number of links
 // with a segment or -1 when the layout does not apply
 int tree_link_positions(const figh_model_s *m, int mode, int flags, int ft_mask, int *pos);

@@ -16,6 +16,7 @@ import numpy as np
 
 from .. import _lib
 from .._host import host_tail, singular_values_batch
+from . import regressor
 from .regressor import _samples_to_device, regressor_flags
 
 
@@ -102,3 +103,43 @@ def objective_cond_batch(robot, trajectories, param, idx_e, idx_base, R_stack=No
     R = base_regressor_triangles_batch(robot, trajectories, param, idx_e, idx_base, R_stack, coupling)
     s = singular_values_batch(R)
     return (s.max(axis=1) / s.min(axis=1)).tolist()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Effort constraints of the same loop (examples/tiago/utils/cubic_spline.py:448-455, called from
+# examples/tiago/optimal_trajectory.py:154 and :288; the constraint Jacobian is taken by finite differences, :321-327, so
+# it runs once per perturbed trajectory): pin.rnea per sample, i.e. W . phi without friction / inertia / offset columns.
+def _rigid_body_param(param):
+    return dict(param, is_joint_torques=True, is_external_wrench=False, has_friction=False, has_actuator_inertia=False,
+                has_joint_offset=False, device_resident=False)
+
+
+def calc_torque(N, robot, q, v, a, param):
+    """``tau[j * N + i] = pin.rnea(model, data, q[i], v[i], a[i])[j]`` (cubic_spline.py:448-455) in one device launch."""
+    p = _rigid_body_param(param)
+    q, v, a = (np.asarray(x, dtype=np.float64)[:N] for x in (q, v, a))
+    phi = np.array(list(robot.get_standard_parameters(p).values()), dtype=np.float64)
+    return regressor.regressor_times_parameters(robot, q, v, a, p, phi)
+
+
+def split_batch(tau, B, rows_per_sample, n_per):
+    """tau of B trajectories of n_per samples evaluated back to back (row j * B n_per + b n_per + i) -> (B, rows n_per), row
+    b in calc_torque's layout (j * n_per + i)."""
+    tau = np.asarray(tau).reshape(rows_per_sample, B, n_per)
+    return np.ascontiguousarray(tau.transpose(1, 0, 2)).reshape(B, rows_per_sample * n_per)
+
+
+def calc_torque_batch(robot, trajectories, param):
+    """``calc_torque`` of B trajectories ``[(q_b, v_b, a_b), ...]`` of equal length in ONE launch: a (B, nv * n_per) array,
+    row b what ``calc_torque(n_per, robot, q_b, v_b, a_b, param)`` returns -- the effort constraints at the B perturbed
+    trajectories of one finite-difference Jacobian, next to :func:`objective_cond_batch`."""
+    if len(trajectories) == 0:
+        raise ValueError("no trajectory given")
+    n_per = len(trajectories[0][0])
+    if n_per == 0 or any(len(t[0]) != n_per or len(t[1]) != n_per or len(t[2]) != n_per for t in trajectories):
+        raise ValueError("the trajectories of a batch must have the same, non-zero number of samples")
+    q = np.concatenate([np.asarray(t[0], dtype=np.float64) for t in trajectories])
+    v = np.concatenate([np.asarray(t[1], dtype=np.float64) for t in trajectories])
+    a = np.concatenate([np.asarray(t[2], dtype=np.float64) for t in trajectories])
+    B = len(trajectories)
+    return split_batch(calc_torque(B * n_per, robot, q, v, a, param), B, robot.model.nv, n_per)

@@ -79,6 +79,69 @@ def build_regressor_basic(robot, q, v, a, param, tau=None):
     return W if param.get("device_resident") else W.numpy()
 
 
+def expand_parameters(phi, ncols, cols=None):
+    """phi over all ``ncols`` reference columns: ``phi`` itself, or -- with ``cols``, an index list into the reference's
+    columns such as ``excitation.base_columns(...)`` -- its entries scattered to those columns and zero elsewhere
+    (tau_base = np.dot(W_b, phi_b), examples/staubli_TX40/identification.py:244)."""
+    phi = np.ascontiguousarray(phi, dtype=np.float64).reshape(-1)
+    if cols is None:
+        if phi.shape != (ncols,):
+            raise ValueError("phi has %d entries, the regressor has %d columns" % (len(phi), ncols))
+        return phi
+    cols = np.asarray(cols, dtype=np.int64).reshape(-1)
+    if phi.shape != cols.shape:
+        raise ValueError("phi has %d entries for %d columns" % (len(phi), len(cols)))
+    if len(cols) and (cols.min() < 0 or cols.max() >= ncols or len(np.unique(cols)) != len(cols)):
+        raise ValueError("cols must be distinct column indices below %d" % ncols)
+    full = np.zeros(ncols)
+    full[cols] = phi
+    return full
+
+
+def regressor_times_parameters_device(robot, d_q, d_v, d_a, N, param, phi, coupling=False, extra_flags=0):
+    """Device-to-device core of :func:`regressor_times_parameters`: DeviceArray tau (rows_per_sample * N) = W . phi for
+    ``phi`` over all columns.  One launch of ``figh_regressor_apply``, W never formed; where the library does not serve the
+    shape (external wrench on a fixed base, tile-blocked inputs) W is built and multiplied (``figh_matvec``)."""
+    mode, flags, ft_mask = regressor_flags(param, coupling)
+    flags |= extra_flags
+    handle = robot.device_model()
+    rows_per_sample, ncols = handle.shape(mode, flags)
+    d_phi = _lib.DeviceArray.from_host(expand_parameters(phi, ncols))
+    d_tau = _lib.DeviceArray((rows_per_sample * N,), np.float64)
+    if not _lib.regressor_apply(handle, mode, flags, ft_mask, N, d_q, d_v, d_a, d_phi, d_tau):
+        W, _ = build_regressor_device(robot, d_q, d_v, d_a, N, param, coupling, extra_flags=extra_flags)
+        _lib.matvec(W.buf, W.rows, W.ld, None, ncols, d_phi, d_tau)
+    return d_tau
+
+
+def _times_parameters(robot, q, v, a, param, phi, coupling):
+    """Host samples -> DeviceArray tau (the one place where the mirrors of this package enter the device)."""
+    N, d_q, d_v, d_a = _samples_to_device(robot.model, q, v, a)
+    return regressor_times_parameters_device(robot, d_q, d_v, d_a, N, param, phi, coupling)
+
+
+def regressor_shape(robot, param, coupling=False):
+    """(rows_per_sample, ncols) of build_regressor_basic's W from the model alone (regressor.py:46, :90, :198-227)."""
+    m = robot.model
+    if param["is_joint_torques"]:
+        rows = m.nv
+    elif param["is_external_wrench"]:
+        rows = 6
+    else:
+        raise UnboundLocalError("local variable 'W_mod' referenced before assignment")
+    return rows, 14 * (m.njoints - 1) + (3 if coupling else 0)
+
+
+def regressor_times_parameters(robot, q, v, a, param, phi, coupling=False, cols=None):
+    """``np.dot(build_regressor_basic(robot, q, v, a, param), phi)`` without the regressor: tau as a float64 array of
+    rows_per_sample * N entries, row j*N + i (a ``DeviceArray`` with ``param["device_resident"]``).  ``phi`` has one entry per
+    column (plus three with ``coupling``, regressor.py:198-227); with ``cols`` it has ``len(cols)`` entries for those columns
+    and the others count as zero -- tau_base = np.dot(W_b, phi_b) for ``cols = excitation.base_columns(...)``."""
+    _, ncols = regressor_shape(robot, param, coupling)
+    d_tau = _times_parameters(robot, q, v, a, param, expand_parameters(phi, ncols, cols), coupling)
+    return d_tau if param.get("device_resident") else d_tau.to_host()
+
+
 def add_coupling_TX40(W, model, data, N, nq, nv, njoints, q, v, a):
     """Append the [Iam6, fvm6, fsm6] columns of the Staubli TX40 wrist coupling (regressor.py:198-227)."""
     v = np.ascontiguousarray(v, dtype=np.float64)

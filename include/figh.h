@@ -91,7 +91,7 @@ typedef struct figh_model_s *figh_model_t;
  * (round 5 did so for figh_tsqr_selected_wrench / figh_regressor_build_padded without a bump: a library of the older ABI
  * accepts the longer argument list under cdecl and silently ignores the new arguments).  figaroh_plus_amd/_lib.py refuses a
  * library -- in-tree or FIGH_LIB_PATH -- whose figh_version() differs from the value it was written against. */
-#define FIGH_ABI_VERSION 107
+#define FIGH_ABI_VERSION 108
 int figh_version(void);
 const char *figh_last_error(void);
 int figh_device_count(int *count);
@@ -201,6 +201,23 @@ int figh_regressor_link_layout(figh_model_t model, int mode, int flags, int ft_m
 /* Leading dimension of the force region of FIGH_FLAG_FORCE_COMPACT for (model, mode, flags, ft_mask): 16 * ceil(nlive / 4).
  * FIGH_ERR_UNSUPPORTED when the layout does not apply (see the flag). */
 int figh_regressor_force_layout(figh_model_t model, int mode, int flags, int ft_mask, int64_t *ld_force);
+
+/* figh_regressor_apply: d_tau_out = W(q, v, a) . phi WITHOUT W -- by definition np.dot(W, phi) for the W that
+ * figh_regressor_build returns for the same (model, mode, flags, ft_mask, q, v, a), row j*N + i, rows_per_sample * N entries;
+ * d_phi holds the ncols entries of figh_regressor_shape in the reference's column numbering.  Replaces the pin.rnea loops
+ * and the friction / actuator-inertia / offset statements of get_torque_rand (src/figaroh/tools/randomdata.py:93-147), of
+ * calc_torque (examples/tiago/utils/cubic_spline.py:448-455: the effort constraints of every trajectory that
+ * examples/tiago/optimal_trajectory.py:154 and :288 evaluate) and tau_base = np.dot(W_b, phi_b) on a fresh trajectory
+ * (examples/staubli_TX40/identification.py:244).  Recursive Newton-Euler with the link wrench in body-regressor form, O(links)
+ * per sample: 192 B per UR10 sample instead of 2 x 4032 B through W.  The quirks of build_regressor_basic are part of the
+ * definition: the FIGH_FLAG_TX40 coupling columns; np.sign(0) = 0; in external-wrench mode massless bodies and the rows
+ * outside ft_mask carry no inertial term, and the Ia / fv / fs / off columns act on all six rows with v[i, k], a[i, k] of link
+ * index k (regressor.py:142-169).  The entries of d_phi that belong to a flag that is off are not read.  No atomics: two calls
+ * give the same bits.  FIGH_ERR_UNSUPPORTED (nothing launched, figh_last_error says why): external-wrench mode on a model
+ * whose first joint is not a free-flyer; FIGH_FLAG_BLOCKED_INPUTS.  Without a HIP device: FIGH_ERR_NO_DEVICE, before any
+ * argument is looked at. */
+int figh_regressor_apply(figh_model_t model, int mode, int flags, int ft_mask, int64_t N, const double *d_q,
+                         const double *d_v, const double *d_a, const double *d_phi, double *d_tau_out);
 
 /* figh_repack_samples: d_dst[(t * width + k) * 64 + l] = d_src[min(64 t + l, N - 1) * width + k] -- a sample-major N x width
  * array (q, v or a exactly as the reference holds them) re-laid per tile of 64 samples, value-major inside the tile, the
