@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # FIGH_LIB_PATH: another build of the same ABI (same-box A/B of kernel variants); default is the in-tree library
 LIB_PATH = os.environ.get("FIGH_LIB_PATH") or os.path.join(_HERE, "libfigh.so")
 
-ABI_VERSION = 108  # include/figh.h FIGH_ABI_VERSION: load() refuses a library of another ABI
+ABI_VERSION = 109  # include/figh.h FIGH_ABI_VERSION: load() refuses a library of another ABI
 
 FIGH_OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_ALLOC, ERR_UNSUPPORTED, ERR_COMM = -1, -2, -3, -4, -5
@@ -112,6 +112,10 @@ SIGNATURES = {
     "figh_filtfilt_cols": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int, _c_double_p, _c_double_p,
                                      C.c_int, C.c_int, _c_double_p, C.c_int, C.c_int, C.c_void_p, C.c_int64,
                                      C.POINTER(C.c_int64)]),
+    "figh_medfilt_cols": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64]),
+    "figh_joint_difference": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
+    "figh_gradient_cols": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                                     C.c_int64]),
     "figh_comm_available": (C.c_int, []),
     "figh_comm_unique_id": (C.c_int, [C.c_void_p]),
     "figh_comm_init": (C.c_int, [C.c_int, C.c_int, C.c_void_p]),
@@ -484,6 +488,28 @@ def filtfilt_cols(d_X, rows, cols, ldx, nblocks, form, b, a, zi, padlen, q, d_Y,
                                     a.ctypes.data_as(_c_double_p), nsec, order, zi.ctypes.data_as(_c_double_p), padlen, q,
                                     d_Y.ptr, ldy, C.byref(out)))
     return out.value
+
+
+def medfilt_cols(X_ptr, rows, cols, ldx, nblocks, kernel_size, Y_ptr, ldy):
+    """scipy.signal.medfilt of every (row block, column) sequence (figh_medfilt_cols), on raw device addresses."""
+    check(load().figh_medfilt_cols(X_ptr, rows, cols, ldx, nblocks, kernel_size, Y_ptr, ldy))
+
+
+def joint_difference_tile(nq, nv):
+    """Sample pairs per LDS tile of figh_joint_difference (the rule of csrc/figh_differentiate.hip difference_tile)."""
+    per_row = 8 * ((nq | 1) + (nv | 1))
+    return 64 * min(4, (65536 - 8 * (nq | 1)) // (64 * per_row))
+
+
+def joint_difference(model, N, q_ptr, ts, dt_ptr, dq_ptr):
+    """dq[i] = difference(model, q[i], q[i + 1]) / (dt[i] or ts), i < N - 1 (figh_joint_difference); ``dt_ptr`` None or the
+    address of N - 1 doubles."""
+    check(load().figh_joint_difference(model.handle, N, q_ptr, float(ts), dt_ptr, dq_ptr))
+
+
+def gradient_cols(F_ptr, rows, cols, ld, ncols_active, h, h_ptr, G_ptr, ldg):
+    """np.gradient(F[:, c], edge_order=1) / (h_ptr[row] or h) for c < ncols_active, +0.0 behind (figh_gradient_cols)."""
+    check(load().figh_gradient_cols(F_ptr, rows, cols, ld, ncols_active, float(h), h_ptr, G_ptr, ldg))
 
 
 def compact_rows(W_ptr, rows, cols, ldw, tau_ptr, key_col, threshold, Wout_ptr, ld_out, tauout_ptr):

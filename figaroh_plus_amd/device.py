@@ -76,6 +76,15 @@ class GpuMatrix:
             raise ValueError("expected a 2-D array, got shape %r" % (arr.shape,))
         return cls(_lib.DeviceArray.from_host(arr.reshape(-1)), arr.shape[0], arr.shape[1])
 
+    def dense(self):
+        """This matrix when its rows are contiguous (``ld == cols``), else a dense copy made on the device (one
+        figh_place_block)."""
+        if self.ld == self.cols or not self.rows:
+            return self if self.ld == self.cols else GpuMatrix(self.buf, self.rows, self.cols, self.cols)
+        out = GpuMatrix.empty(self.rows, self.cols)
+        _lib.place_block(self.ptr, self.ld, self.rows, self.cols, 1.0, out.ptr, out.cols)
+        return out
+
     def numpy(self):
         if getattr(self, "compact", None) is not None:
             # (IdentificationPipeline(w_layout="block-compact"): rows / cols describe the regressor, the buffer holds

@@ -288,7 +288,13 @@ def joint_difference(model, q0, q1):
 def calculate_first_second_order_differentiation(model, q, param, dt=None):
     """(q, dq, ddq) by finite differences -- identification_tools.py:334-387, including its conventions: forward
     difference for dq, ``np.gradient`` of dq for ddq on joints ``range(model.nq - 1)`` only (the last joint's
-    acceleration stays 0 for fixed-base robots), two samples dropped from q and one from dq / ddq."""
+    acceleration stays 0 for fixed-base robots), two samples dropped from q and one from dq / ddq.
+
+    A ``GpuMatrix`` q, or ``param["device_resident"]``, takes the device path (figh_joint_difference +
+    figh_gradient_cols): three ``GpuMatrix`` come back, prefixes of their buffers, ready for ``build_regressor_basic`` /
+    ``IdentificationPipeline.set_samples`` without a copy."""
+    if isinstance(q, GpuMatrix) or param.get("device_resident"):
+        return _differentiate_device(model, q, param, dt)
     q = np.asarray(q, dtype=np.float64)
     ncol = q.shape[1] if param["is_joint_torques"] else q.shape[1] - 1
     if param["is_external_wrench"]:
@@ -308,6 +314,76 @@ def calculate_first_second_order_differentiation(model, q, param, dt=None):
     return q[:-2], dq[:-1], ddq[:-1]
 
 
+def _divisor_to_device(h, count, what):
+    """(scalar, device address or None, keep-alive) of a divisor that is a number or one value per row."""
+    if isinstance(h, _lib.DeviceArray) or hasattr(h, "ptr"):
+        if getattr(h, "size", count) != count:
+            raise ValueError("%s must have %d entries, got %d" % (what, count, h.size))
+        return 0.0, h.ptr, h
+    if np.ndim(h) == 0:
+        return float(h), None, None
+    h = np.ascontiguousarray(h, dtype=np.float64).reshape(-1)
+    if h.shape[0] != count:
+        raise ValueError("%s must have %d entries, got %d" % (what, count, h.shape[0]))
+    d_h = _lib.DeviceArray.from_host(h)
+    return 0.0, d_h.ptr, d_h
+
+
+def _differentiate_device(model, q, param, dt):
+    """calculate_first_second_order_differentiation with q, dq and ddq resident: dq = difference(q[i], q[i + 1]) / ts for
+    every joint type (identification_tools.py:366-376), ddq = np.gradient(dq) / ts on the columns ``range(model.nq - 1)``
+    (:378-384), ``dt`` per pair for dq and the same array per row for ddq, as in the reference."""
+    q = to_device(q)[0].dense()
+    N = q.rows
+    if q.cols != model.nq:
+        raise ValueError("q must have nq = %d columns, got %d" % (model.nq, q.cols))
+    if N < 3:
+        raise ValueError("Shape of array too small to calculate a numerical gradient, at least (edge_order + 1) elements "
+                         "are required.")
+    ts, dt_ptr, keep = (float(param["ts"]), None, None) if dt is None else _divisor_to_device(dt, N - 1, "dt")
+    handle = _lib.ModelHandle(model.to_flat())
+    dq, ddq = GpuMatrix.empty(N - 1, model.nv), GpuMatrix.empty(N - 1, model.nv)
+    _lib.joint_difference(handle, N, q.ptr, ts, dt_ptr, dq.ptr)
+    _lib.gradient_cols(dq.ptr, N - 1, model.nv, model.nv, min(model.nq - 1, model.nv), ts, dt_ptr, ddq.ptr, model.nv)
+    del keep
+    return GpuMatrix(q.buf, N - 2, model.nq), GpuMatrix(dq.buf, N - 2, model.nv), GpuMatrix(ddq.buf, N - 2, model.nv)
+
+
+def median_filter_columns(data, kernel_size):
+    """``signal.medfilt(data[:, c], kernel_size)`` of every column -- the first statement of the TIAGo script's
+    ``apply_filters`` (examples/tiago/identification.py:63-90) -- on the device (figh_medfilt_cols).  A host array comes
+    back as a host array of the same shape, a ``GpuMatrix`` as a ``GpuMatrix``."""
+    kernel_size = int(kernel_size)
+    if kernel_size % 2 != 1:
+        raise ValueError("Each element of kernel_size should be odd.")
+    on_device = isinstance(data, GpuMatrix)
+    if on_device:
+        X = data
+    else:
+        data = np.asarray(data, dtype=np.float64)
+        X = GpuMatrix.from_host(data.reshape(data.shape[0], -1))
+    out = GpuMatrix.empty(X.rows, X.cols)
+    _lib.medfilt_cols(X.ptr, X.rows, X.cols, X.ld, 1, kernel_size, out.ptr, out.cols)
+    return out if on_device else out.numpy().reshape(data.shape)
+
+
+def gradient_columns(x, h):
+    """``np.gradient(x[:, c], edge_order=1) / h`` of every column, ``h`` a number or one value per row (figh_gradient_cols).
+    With ``h = np.gradient(t)`` this is the TIAGo script's ``estimate_acceleration``
+    (examples/tiago/identification.py:92-99).  Host array in, host array out; ``GpuMatrix`` in, ``GpuMatrix`` out."""
+    on_device = isinstance(x, GpuMatrix)
+    if on_device:
+        X = x
+    else:
+        x = np.asarray(x, dtype=np.float64)
+        X = GpuMatrix.from_host(x.reshape(x.shape[0], -1))
+    hs, h_ptr, keep = _divisor_to_device(h, X.rows, "h")
+    out = GpuMatrix.empty(X.rows, X.cols)
+    _lib.gradient_cols(X.ptr, X.rows, X.cols, X.ld, X.cols, hs, h_ptr, out.ptr, out.cols)
+    del keep
+    return out if on_device else out.numpy().reshape(x.shape)
+
+
 def _filtfilt_device(x2d, nblocks, form, b, a, zi, padlen, q):
     """Columns of x2d (rows x cols, made of nblocks row blocks) through figh_filtfilt_cols; returns (rows_out, cols)."""
     x2d = np.ascontiguousarray(x2d, dtype=np.float64)
@@ -324,12 +400,23 @@ def _filtfilt_device(x2d, nblocks, form, b, a, zi, padlen, q):
 def low_pass_filter_data(data, param, nbutter=5):
     """Zero-phase Butterworth low-pass + border trimming -- identification_tools.py:390-424.  The filter is designed
     on the host (``signal.butter`` / ``lfilter_zi``: a dozen numbers); the forward-backward recursion over every column
-    runs on the device, operation by operation as ``signal.filtfilt(b, a, data, padtype='odd', padlen=...)``."""
+    runs on the device, operation by operation as ``signal.filtfilt(b, a, data, padtype='odd', padlen=...)``.  A
+    ``GpuMatrix`` comes back as a ``GpuMatrix`` (no copy to the host)."""
     from scipy import signal
 
     cutoff = param["ts"] * param["cut_off_frequency_butterworth"] / 2
     b, a = signal.butter(nbutter, cutoff, "low")
     padlen = 3 * (max(len(b), len(a)) - 1)
+    if isinstance(data, GpuMatrix):  # stays in HBM: the trimmed result is a window of the filtered buffer
+        if data.rows <= padlen:
+            raise ValueError("The length of the input vector x must be greater than padlen, which is %d." % padlen)
+        b, a = b / a[0], a / a[0]
+        d_y = _lib.DeviceArray((data.rows * data.cols,), np.float64)
+        _lib.filtfilt_cols(data.buf, data.rows, data.cols, data.ld, 1, 1, b, a, signal.lfilter_zi(b, a), padlen, 1, d_y,
+                           data.cols)
+        nbord = 5 * nbutter
+        kept = max(data.rows - 2 * nbord, 0)  # (nothing left: an empty window at the start of the buffer, not past its end)
+        return GpuMatrix(_DevView(d_y, 8 * nbord * data.cols if kept else 0), kept, data.cols)
     data = np.asarray(data, dtype=np.float64)
     x2d = data.reshape(data.shape[0], -1)
     if x2d.shape[0] <= padlen:

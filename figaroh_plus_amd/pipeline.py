@@ -157,7 +157,8 @@ class IdentificationPipeline:
 
     # ------------------------------------------------------------------ inputs
     def set_samples(self, q, v, a, tau=None):
-        """Upload this rank's samples (q: N x nq, v/a: N x nv) and optionally tau (rows of W,).
+        """Upload this rank's samples (q: N x nq, v/a: N x nv) and optionally tau (rows of W,).  ``GpuMatrix`` q, v, a
+        (calculate_first_second_order_differentiation's device output) and a device vector tau are taken where they are.
 
         Shapes are checked here, before anything reaches the device: the kernels index q, v, a and tau with N and the
         model's nq / nv, so a mismatched array would be read past its HBM allocation."""
@@ -170,7 +171,14 @@ class IdentificationPipeline:
             rps_in = len(self.row_blocks)
         else:
             rps_in = rps
-        if tau is not None:
+        tau_resident = tau is not None and (isinstance(tau, _lib.DeviceArray) or hasattr(tau, "ptr"))
+        if tau_resident:  # a device vector of the caller's (decimate_joint_blocks / reject_rows output): used as it is
+            if self.row_blocks is not None:
+                raise NotImplementedError("row_blocks: tau is re-laid per active dof on the host; pass a host array")
+            if int(tau.size) != rps_in * len(q):
+                raise ValueError("tau must have rows_per_sample * N = %d * %d = %d entries; got %d"
+                                 % (rps_in, len(q), rps_in * len(q), int(tau.size)))
+        elif tau is not None:
             tau = np.ascontiguousarray(tau, dtype=np.float64).reshape(-1)
             if tau.shape[0] != rps_in * len(q):
                 raise ValueError("tau must have rows_per_sample * N = %d * %d = %d entries; got %d"
@@ -181,7 +189,9 @@ class IdentificationPipeline:
                     full[b * len(q):(b + 1) * len(q)] = tau[i * len(q):(i + 1) * len(q)]
                 tau = full
         N, d_q, d_v, d_a = _samples_to_device(self.robot.model, q, v, a)  # raises ValueError on a shape mismatch
-        d_tau = None if tau is None else _lib.DeviceArray.from_host(tau)
+        d_tau = None if tau is None else tau if tau_resident else _lib.DeviceArray.from_host(tau)
+        # buffers of GpuMatrix arguments stay the caller's: only what this call allocated is freed after the repack
+        borrowed = [x.buf for x in (q, v, a) if isinstance(x, GpuMatrix)]
         # Tree models: the generic regressor kernel takes one sample per lane, and in the reference's sample-major arrays a
         # lane's values lie nq * 8 bytes from its neighbour's.  The three arrays are re-laid once per tile of 64 samples,
         # value-major (figh_repack_samples); K1' then reads one 512-byte line per value.  Chains keep the original arrays
@@ -196,7 +206,8 @@ class IdentificationPipeline:
             _lib.synchronize()
             self.repack_ms = 1e3 * (time.perf_counter() - t0)
             for d in (d_q, d_v, d_a):
-                d.free()
+                if not any(d is b for b in borrowed):
+                    d.free()
             d_q, d_v, d_a = blocked
             self._in_flags = _lib.FLAG_BLOCKED_INPUTS
             if self.chunk_samples:

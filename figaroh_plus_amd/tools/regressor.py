@@ -44,15 +44,19 @@ def regressor_flags(param, coupling=False):
 
 
 def _samples_to_device(model, q, v, a):
-    q = np.ascontiguousarray(q, dtype=np.float64)
-    v = np.ascontiguousarray(v, dtype=np.float64)
-    a = np.ascontiguousarray(a, dtype=np.float64)
+    """(N, d_q, d_v, d_a).  Host arrays are uploaded; a ``GpuMatrix`` (the device differentiation's output) passes its own
+    buffer through -- it stays the caller's -- or, with a padded leading dimension, a dense copy made on the device."""
+    def one(x, width):
+        if isinstance(x, GpuMatrix):
+            return x.shape, x.dense().buf
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        return x.shape, (x if x.ndim == 2 and x.shape[1] == width else None)
+
     N = len(q)
-    if q.shape != (N, model.nq) or v.shape != (N, model.nv) or a.shape != (N, model.nv):
-        raise ValueError("q, v, a must have shapes (N, nq), (N, nv), (N, nv); got %r %r %r"
-                         % (q.shape, v.shape, a.shape))
-    return N, _lib.DeviceArray.from_host(q.reshape(-1)), _lib.DeviceArray.from_host(v.reshape(-1)), \
-        _lib.DeviceArray.from_host(a.reshape(-1))
+    (sq, bq), (sv, bv), (sa, ba) = one(q, model.nq), one(v, model.nv), one(a, model.nv)
+    if sq != (N, model.nq) or sv != (N, model.nv) or sa != (N, model.nv):
+        raise ValueError("q, v, a must have shapes (N, nq), (N, nv), (N, nv); got %r %r %r" % (sq, sv, sa))
+    return (N,) + tuple(_lib.DeviceArray.from_host(b.reshape(-1)) if isinstance(b, np.ndarray) else b for b in (bq, bv, ba))
 
 
 def build_regressor_device(robot, d_q, d_v, d_a, N, param, coupling=False, colsq=False, extra_flags=0):

@@ -91,7 +91,7 @@ typedef struct figh_model_s *figh_model_t;
  * (round 5 did so for figh_tsqr_selected_wrench / figh_regressor_build_padded without a bump: a library of the older ABI
  * accepts the longer argument list under cdecl and silently ignores the new arguments).  figaroh_plus_amd/_lib.py refuses a
  * library -- in-tree or FIGH_LIB_PATH -- whose figh_version() differs from the value it was written against. */
-#define FIGH_ABI_VERSION 108
+#define FIGH_ABI_VERSION 109
 int figh_version(void);
 const char *figh_last_error(void);
 int figh_device_count(int *count);
@@ -435,6 +435,39 @@ int figh_regressor_gram(figh_model_t model, int mode, int flags, int ft_mask, in
 int figh_filtfilt_cols(const double *d_X, int64_t rows, int cols, int64_t ldx, int nblocks, int form, const double *h_b,
                        const double *h_a, int nsec, int order, const double *h_zi, int padlen, int q, double *d_Y,
                        int64_t ldy, int64_t *rows_out);
+
+/* ------------------------------------------------------------------ median filter and finite differences
+ * The device front end of the real-data chain: raw joint positions go in once, (q, dq, ddq) come out resident in the
+ * layouts K1 reads.  All three entries are parallel in time; the translation unit is compiled without FMA contraction.
+ *
+ * figh_medfilt_cols: scipy.signal.medfilt(x, kernel_size) of every (row block, column) sequence of d_X (rows x cols, ldx;
+ * nblocks row blocks of rows / nblocks samples) -- the first statement of the TIAGo script's apply_filters
+ * (examples/tiago/identification.py:63-90).  Zero padding at both ends OF EACH BLOCK, the median is an element of the
+ * window: equal to SciPy on data without NaN (np.array_equal; where the window holds zeros of both signs the median may
+ * be the other signed zero than SciPy's sort picks).  kernel_size: odd, 1 .. 63 (1 - 9 sort the window in registers, larger
+ * ones in a run-time loop); an even size, a size outside [1, 63], a leading dimension below cols or rows % nblocks != 0:
+ * FIGH_ERR_INVALID, nothing launched. */
+int figh_medfilt_cols(const double *d_X, int64_t rows, int cols, int64_t ldx, int nblocks, int kernel_size, double *d_Y,
+                      int64_t ldy);
+/* figh_joint_difference: d_dq[i, :] = pin.difference(model, q[i], q[i + 1]) / (d_dt ? d_dt[i] : ts), i = 0 .. N - 2 -- the
+ * loop of calculate_first_second_order_differentiation (identification_tools.py:366-376; call sites
+ * examples/ur10/identification.py:122, examples/staubli_TX40/identification.py:145, examples/human/identification.py:424).
+ * d_q: N x nq row-major, d_dq: (N - 1) x nv row-major, d_dt: NULL or N - 1 doubles.  Revolute / prismatic: q1 - q0
+ * (bit-equal to np.diff(q) / ts); continuous (cos, sin): atan2(s1 c0 - c1 s0, c1 c0 + s1 s0); free-flyer (p, quaternion
+ * xyzw): log6(R0^T R1, R0^T (p1 - p0)), (linear, angular), with the branches theta < 1e-8, pi - theta < 1e-6 (log3) and
+ * t < 1e-4 (log6) and the operation order of the package's host mirror, so that the device differs from it only through
+ * acos, atan2, sin, cos, sqrt.  Tiles of 64 k sample pairs (k = the largest of 1 .. 4 for which (64 k + 1) rows of q and
+ * 64 k rows of dq, row strides padded to odd, fit 64 KB of LDS) are staged in LDS; a chain model never runs the per-pair
+ * pass.  Row N of d_q is never read.  N >= 2. */
+int figh_joint_difference(figh_model_t model, int64_t N, const double *d_q, double ts, const double *d_dt, double *d_dq);
+/* figh_gradient_cols: d_G[:, c] = np.gradient(d_F[:, c], edge_order=1) / (d_h ? d_h[row] : h) for c < ncols_active
+ * (identification_tools.py:378-384; np.gradient(dq) / np.gradient(t) of examples/tiago/identification.py:92-99 with
+ * d_h = np.gradient(t)): (F[i+1] - F[i-1]) / 2.0 inside, F[1] - F[0] and F[n-1] - F[n-2] at the ends, then one division --
+ * bit-equal to NumPy.  Columns c >= ncols_active of d_G are written as +0.0 (the reference's range(model.nq - 1): the last
+ * joint of a fixed-base robot keeps a zero acceleration).  rows >= 2 (np.gradient raises below that), d_h: NULL or rows
+ * doubles. */
+int figh_gradient_cols(const double *d_F, int64_t rows, int cols, int64_t ld, int ncols_active, double h, const double *d_h,
+                       double *d_G, int64_t ldg);
 
 /* ------------------------------------------------------------------ multi-GPU (RCCL over xGMI), SURVEY.md section 8e
  * One process per GPU.  Rank 0 calls figh_comm_unique_id and ships the 128 bytes to the other ranks by any
