@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # FIGH_LIB_PATH: another build of the same ABI (same-box A/B of kernel variants); default is the in-tree library
 LIB_PATH = os.environ.get("FIGH_LIB_PATH") or os.path.join(_HERE, "libfigh.so")
 
-ABI_VERSION = 109  # include/figh.h FIGH_ABI_VERSION: load() refuses a library of another ABI
+ABI_VERSION = 110  # include/figh.h FIGH_ABI_VERSION: load() refuses a library of another ABI
 
 FIGH_OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_ALLOC, ERR_UNSUPPORTED, ERR_COMM = -1, -2, -3, -4, -5
@@ -116,6 +116,12 @@ SIGNATURES = {
     "figh_joint_difference": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
     "figh_gradient_cols": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
                                      C.c_int64]),
+    "figh_spline_sample": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_double, _c_int32_p, _c_int32_p,
+                                     _c_double_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                     C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]),
+    "figh_excitation_constraints": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, _c_int32_p, _c_int32_p, C.c_int,
+                                              _c_int32_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                              C.c_void_p, C.c_int64]),
     "figh_comm_available": (C.c_int, []),
     "figh_comm_unique_id": (C.c_int, [C.c_void_p]),
     "figh_comm_init": (C.c_int, [C.c_int, C.c_int, C.c_void_p]),
@@ -510,6 +516,33 @@ def joint_difference(model, N, q_ptr, ts, dt_ptr, dq_ptr):
 def gradient_cols(F_ptr, rows, cols, ld, ncols_active, h, h_ptr, G_ptr, ldg):
     """np.gradient(F[:, c], edge_order=1) / (h_ptr[row] or h) for c < ncols_active, +0.0 behind (figh_gradient_cols)."""
     check(load().figh_gradient_cols(F_ptr, rows, cols, ld, ncols_active, float(h), h_ptr, G_ptr, ldg))
+
+
+def spline_sample(model, B, n_wps, n_per, freq, act_idxq, act_idxv, tps, d_wps, d_vel_wps, vel_stride, d_acc_wps, acc_stride,
+                  d_q0, q_ptr, ldq, v_ptr, a_ptr, ldv):
+    """B waypoint sets -> full-configuration samples back to back (figh_spline_sample); the outputs are raw device addresses
+    (windows of padded buffers), ``vel_stride`` / ``acc_stride`` 0 for one set of velocity / acceleration waypoints."""
+    iq, iv, tps = _i32(act_idxq), _i32(act_idxv), _f64(tps).reshape(-1)
+    if len(tps) != n_wps or len(iv) != len(iq) or d_wps.size < B * len(iq) * n_wps or d_q0.size < model.nq:
+        raise ValueError("spline_sample: %d time points, %d / %d active indices and %d waypoint entries for B = %d, n_wps = %d"
+                         % (len(tps), len(iq), len(iv), d_wps.size, B, n_wps))
+    for d, stride in ((d_vel_wps, vel_stride), (d_acc_wps, acc_stride)):
+        if d.size < (B - 1) * stride + len(iq) * n_wps:
+            raise ValueError("spline_sample: a velocity / acceleration waypoint buffer is shorter than its stride asks for")
+    check(load().figh_spline_sample(model.handle, B, n_wps, len(iq), n_per, float(freq), iq.ctypes.data_as(_c_int32_p),
+                                    iv.ctypes.data_as(_c_int32_p), tps.ctypes.data_as(_c_double_p), d_wps.ptr, d_vel_wps.ptr,
+                                    vel_stride, d_acc_wps.ptr, acc_stride, d_q0.ptr, q_ptr, ldq, v_ptr, a_ptr, ldv))
+
+
+def excitation_constraints(model, B, n_per, act_idxq, act_idxv, idx_waypoints, q_ptr, ldq, v_ptr, ldv, d_tau, out_ptr, ld_out):
+    """Row b of out = concatenate((q_wp, v_act, tau_act), axis=None) of trajectory b (figh_excitation_constraints)."""
+    iq, iv, iw = _i32(act_idxq), _i32(act_idxv), _i32(idx_waypoints).reshape(-1)
+    if len(iv) != len(iq) or d_tau.size < model.nv * B * n_per:
+        raise ValueError("excitation_constraints: %d / %d active indices, tau of %d entries for %d x %d samples of %d efforts"
+                         % (len(iq), len(iv), d_tau.size, B, n_per, model.nv))
+    check(load().figh_excitation_constraints(model.handle, B, n_per, len(iq), iq.ctypes.data_as(_c_int32_p),
+                                             iv.ctypes.data_as(_c_int32_p), len(iw), iw.ctypes.data_as(_c_int32_p), q_ptr, ldq,
+                                             v_ptr, ldv, d_tau.ptr, out_ptr, ld_out))
 
 
 def compact_rows(W_ptr, rows, cols, ldw, tau_ptr, key_col, threshold, Wout_ptr, ld_out, tauout_ptr):

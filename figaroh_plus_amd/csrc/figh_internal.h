@@ -118,6 +118,8 @@ enum WorkspaceSlot {
     kWsBlocksMidTri,        // figh_tsqr_selected_blocks: level-0 triangles of the mid blocks
     kWsFusedBatchTri,       // figh_regressor_tsqr_batch_fused: the consumers' triangles of every workgroup
     kWsDynamicsState,       // figh_regressor_apply (tree kernel): per-wave link wrenches and transforms
+    kWsSplineTable,         // figh_spline_sample: segment coefficients, local times, time points, segment indices
+    kWsConstraintIdx,       // figh_excitation_constraints: the waypoint sample indices
     kWorkspaceSlots
 };
 

@@ -57,8 +57,32 @@ def objective_cond(robot, q, v, a, param, idx_e, idx_base, R_stack=None, couplin
     return float(s.max() / s.min())
 
 
+def _batch_lists(trajectories):
+    """[(q_b, v_b, a_b), ...] of equal length -> (B, n_per, q, v, a) with the trajectories back to back, on the host."""
+    if len(trajectories) == 0:
+        raise ValueError("no trajectory given")
+    n_per = len(trajectories[0][0])
+    if n_per == 0 or any(len(t[0]) != n_per or len(t[1]) != n_per or len(t[2]) != n_per for t in trajectories):
+        raise ValueError("the trajectories of a batch must have the same, non-zero number of samples")
+    q = np.concatenate([np.asarray(t[0], dtype=np.float64) for t in trajectories])
+    v = np.concatenate([np.asarray(t[1], dtype=np.float64) for t in trajectories])
+    a = np.concatenate([np.asarray(t[2], dtype=np.float64) for t in trajectories])
+    return len(trajectories), n_per, q, v, a
+
+
+def _batch_to_device(robot, trajectories):
+    """(B, n_per, d_q, d_v, d_a): a :class:`TrajectoryBatch` passes its resident buffers through, a list is concatenated
+    and uploaded."""
+    if isinstance(trajectories, TrajectoryBatch):
+        t = trajectories
+        return (t.B, t.n_per) + _samples_to_device(robot.model, t.q, t.v, t.a)[1:]
+    B, n_per, q, v, a = _batch_lists(trajectories)
+    return (B, n_per) + _samples_to_device(robot.model, q, v, a)[1:]
+
+
 def base_regressor_triangles_batch(robot, trajectories, param, idx_e, idx_base, R_stack=None, coupling=False):
-    """R factors (B x r x r) of the base regressors of B trajectories ``[(q_b, v_b, a_b), ...]`` of equal length.
+    """R factors (B x r x r) of the base regressors of B trajectories ``[(q_b, v_b, a_b), ...]`` of equal length, or of a
+    :class:`TrajectoryBatch` (resident samples: nothing is concatenated or uploaded).
 
     Serial chains of 5 to 7 joints in joint-torque mode (UR10), r <= 64, at least 64 samples per trajectory: one launch
     that builds and factors every trajectory's regressor tiles in LDS, W never stored, + one to three merge launches,
@@ -72,14 +96,7 @@ def base_regressor_triangles_batch(robot, trajectories, param, idx_e, idx_base, 
     _, ncols = dm.shape(mode, flags)
     cols = base_columns(ncols, idx_e, idx_base)
     r = len(cols)
-    n_per = len(trajectories[0][0])
-    if n_per == 0 or any(len(t[0]) != n_per or len(t[1]) != n_per or len(t[2]) != n_per for t in trajectories):
-        raise ValueError("the trajectories of a batch must have the same, non-zero number of samples")
-    q = np.concatenate([np.asarray(t[0], dtype=np.float64) for t in trajectories])
-    v = np.concatenate([np.asarray(t[1], dtype=np.float64) for t in trajectories])
-    a = np.concatenate([np.asarray(t[2], dtype=np.float64) for t in trajectories])
-    _, d_q, d_v, d_a = _samples_to_device(robot.model, q, v, a)
-    B = len(trajectories)
+    B, n_per, d_q, d_v, d_a = _batch_to_device(robot, trajectories)
     d_idx = _lib.DeviceArray.from_host(cols)
     d_stack = None
     if R_stack is not None:
@@ -132,14 +149,290 @@ def split_batch(tau, B, rows_per_sample, n_per):
 def calc_torque_batch(robot, trajectories, param):
     """``calc_torque`` of B trajectories ``[(q_b, v_b, a_b), ...]`` of equal length in ONE launch: a (B, nv * n_per) array,
     row b what ``calc_torque(n_per, robot, q_b, v_b, a_b, param)`` returns -- the effort constraints at the B perturbed
-    trajectories of one finite-difference Jacobian, next to :func:`objective_cond_batch`."""
-    if len(trajectories) == 0:
-        raise ValueError("no trajectory given")
-    n_per = len(trajectories[0][0])
-    if n_per == 0 or any(len(t[0]) != n_per or len(t[1]) != n_per or len(t[2]) != n_per for t in trajectories):
-        raise ValueError("the trajectories of a batch must have the same, non-zero number of samples")
-    q = np.concatenate([np.asarray(t[0], dtype=np.float64) for t in trajectories])
-    v = np.concatenate([np.asarray(t[1], dtype=np.float64) for t in trajectories])
-    a = np.concatenate([np.asarray(t[2], dtype=np.float64) for t in trajectories])
-    B = len(trajectories)
+    trajectories of one finite-difference Jacobian, next to :func:`objective_cond_batch`.  A :class:`TrajectoryBatch` runs
+    the same launch on its resident samples (bit-equal to the list form of the same arrays); with
+    ``param["device_resident"]`` its tau stays on the device, a ``DeviceArray`` in the batched layout (row
+    j B n_per + b n_per + i) that :func:`constraints_batch` reads."""
+    if isinstance(trajectories, TrajectoryBatch):
+        t = trajectories
+        p = dict(_rigid_body_param(param), device_resident=True)
+        phi = np.array(list(robot.get_standard_parameters(p).values()), dtype=np.float64)
+        d_tau = regressor.regressor_times_parameters(robot, t.q, t.v, t.a, p, phi)
+        return d_tau if param.get("device_resident") else split_batch(d_tau.to_host(), t.B, robot.model.nv, t.n_per)
+    B, n_per, q, v, a = _batch_lists(trajectories)
     return split_batch(calc_torque(B * n_per, robot, q, v, a, param), B, robot.model.nv, n_per)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The trajectories of the same loop (examples/tiago/utils/cubic_spline.py:33-233): waypoints -> samples.  The scripts always
+# pass velocity and acceleration waypoints, so every ndcurves.exact_cubic of get_active_config has two waypoints and four end
+# constraints: the unique quintic through position, velocity and acceleration at both ends.  The functions below state that
+# quintic in the operation order of csrc/figh_trajectory.hip (its header comment), one rounded operation per NumPy call, so
+# that host mirror and kernel are bit-equal.  Parity with ndcurves is mathematical (the same polynomial), not bitwise.
+def spline_times(freq, time_points, n_per=None):
+    """(delta_t, T, N, t, k, u) of get_active_config (:133-142): ``t[i] = tps[0] + i * delta_t``, its segment ``k[i]`` (the
+    largest k with ``tps[k] <= t[i]``, at most n_wps - 2) and local time ``u[i] = min(t[i] - tps[k], tps[k+1] - tps[k])``.
+    ``n_per``: that many samples instead of the reference's N, as ``figh_spline_sample`` takes it -- a prefix below N; above it
+    the samples behind the last time point sit at the end of the last segment."""
+    tps = np.asarray(time_points, dtype=np.float64).reshape(-1)
+    if len(tps) < 2 or not np.all(tps[1:] > tps[:-1]) or not np.isfinite(tps[[0, -1]]).all():
+        raise ValueError("time points must be finite and strictly increasing")
+    delta_t = 1 / freq
+    T = tps[-1] - tps[0]
+    N = int(T / delta_t) + 1
+    t = tps[0] + np.arange(N if n_per is None else n_per, dtype=np.float64) * delta_t
+    k = np.minimum(np.searchsorted(tps, t, side="right") - 1, len(tps) - 2)
+    u = np.minimum(t - tps[k], tps[k + 1] - tps[k])
+    return delta_t, T, N, t, k, u
+
+
+def spline_coefficients(time_points, wps, vel_wps, acc_wps):
+    """c0 .. c5 of every segment: ``wps`` is (..., n_act, n_wps), the result (..., n_act, n_wps - 1, 6)."""
+    tps = np.asarray(time_points, dtype=np.float64).reshape(-1)
+    wps, vel, acc = (np.asarray(x, dtype=np.float64) for x in (wps, vel_wps, acc_wps))
+    h = tps[1:] - tps[:-1]
+    h2 = h * h
+    h3 = h2 * h
+    h4 = h3 * h
+    h5 = h4 * h
+    p0, p1 = wps[..., :-1], wps[..., 1:]
+    v0, v1 = vel[..., :-1], vel[..., 1:]
+    a0, a1 = acc[..., :-1], acc[..., 1:]
+    D = p1 - p0
+    c3 = ((20.0 * D - (8.0 * v1 + 12.0 * v0) * h) - (3.0 * a0 - a1) * h2) / (2.0 * h3)
+    c4 = ((-30.0 * D + (14.0 * v1 + 16.0 * v0) * h) + (3.0 * a0 - 2.0 * a1) * h2) / (2.0 * h4)
+    c5 = ((12.0 * D - (6.0 * (v1 + v0)) * h) - (a0 - a1) * h2) / (2.0 * h5)
+    return np.stack(np.broadcast_arrays(p0, v0, a0 / 2.0, c3, c4, c5), axis=-1)
+
+
+def spline_samples(coef, k, u):
+    """(q, dq, ddq), each (..., N, n_act), of the segments ``coef`` (..., n_act, n_seg, 6) at the samples (k, u)."""
+    c = np.moveaxis(coef[..., k, :], -3, -2)  # (..., N, n_act, 6)
+    u = u[:, None]
+    c0, c1, c2, c3, c4, c5 = (c[..., m] for m in range(6))
+    q = ((((c5 * u + c4) * u + c3) * u + c2) * u + c1) * u + c0
+    dq = ((((5.0 * c5) * u + 4.0 * c4) * u + 3.0 * c3) * u + 2.0 * c2) * u + c1
+    ddq = (((20.0 * c5) * u + 12.0 * c4) * u + 6.0 * c3) * u + 2.0 * c2
+    return q, dq, ddq
+
+
+class CubicSpline:
+    """``CubicSpline`` of examples/tiago/utils/cubic_spline.py:33-233: the same constructor, attributes, ``get_active_config``
+    / ``get_full_config`` / ``check_cfg_constraints``.  Host arrays in, host arrays out through the NumPy mirror above;
+    ``get_full_config(..., device_resident=True)`` returns three ``GpuMatrix`` written by ``figh_spline_sample``.  The time of
+    a sample is capped at the end of its segment: where rounding puts the last sample behind the last time point ndcurves
+    raises, this class evaluates the end of the last segment.  Plotting, waypoint pools and collisions are not mirrored."""
+
+    def __init__(self, robot, num_waypoints, active_joints, soft_lim=0):
+        self.robot = robot
+        self.rmodel = robot.model
+        self.num_waypoints = num_waypoints
+        self.act_Jid = [self.rmodel.getJointId(i) for i in active_joints]
+        self.act_Jname = [self.rmodel.names[jid] for jid in self.act_Jid]
+        self.act_J = [self.rmodel.joints[jid] for jid in self.act_Jid]
+        self.act_idxq = [J.idx_q for J in self.act_J]
+        self.act_idxv = [J.idx_v for J in self.act_J]
+        self.dim_q = (len(self.act_idxq), self.num_waypoints)
+        self.dim_v = (len(self.act_idxv), self.num_waypoints)
+        m = self.rmodel
+        self.upper_q = m.upperPositionLimit[self.act_idxq]
+        self.lower_q = m.lowerPositionLimit[self.act_idxq]
+        self.upper_dq = m.velocityLimit[self.act_idxv]
+        self.lower_dq = -m.velocityLimit[self.act_idxv]
+        self.upper_effort = m.effortLimit[self.act_idxv]
+        self.lower_effort = -m.effortLimit[self.act_idxv]
+        if soft_lim > 0:  # (:64-80: each lower limit is moved by the range that is left after its upper limit moved)
+            self.upper_q = self.upper_q - soft_lim * abs(self.upper_q - self.lower_q)
+            self.lower_q = self.lower_q + soft_lim * abs(self.upper_q - self.lower_q)
+            self.upper_dq = self.upper_dq - soft_lim * abs(self.upper_dq - self.lower_dq)
+            self.lower_dq = self.lower_dq + soft_lim * abs(self.upper_dq - self.lower_dq)
+            self.upper_effort = self.upper_effort - soft_lim * abs(self.upper_effort - self.lower_effort)
+            self.lower_effort = self.lower_effort + soft_lim * abs(self.upper_effort - self.lower_effort)
+
+    def _check(self, waypoints, vel_waypoints, acc_waypoints):
+        pad = " " * 40  # (the reference's messages are string literals continued over a line break)
+        assert self.dim_q == waypoints.shape, "(Pos) Check size " + pad + "(num_active_joints,num_waypoints)!"
+        if vel_waypoints is None or acc_waypoints is None:
+            raise NotImplementedError(
+                "without velocity and acceleration waypoints the reference builds ndcurves' unconstrained exact_cubic, whose "
+                "polynomial is not restated here (ndcurves is not a dependency); pass both, zero arrays included, as the "
+                "scripts do")
+        assert self.dim_v == vel_waypoints.shape, "(Vel) Check size" + pad + "(num_active_joints, num_waypoints)!"
+        assert self.dim_v == acc_waypoints.shape, "(Acc) Check size" + pad + "(num_active_joints, num_waypoints)!"
+        for J, name in zip(self.act_J, self.act_Jname):
+            if J.nq != 1 or J.nv != 1:
+                raise ValueError("active joint %s is not one revolute or prismatic degree of freedom (nq = %d, nv = %d): a "
+                                 "continuous or free-flyer joint has no waypoint in joint coordinates" % (name, J.nq, J.nv))
+
+    def get_active_config(self, freq, time_points, waypoints, vel_waypoints=None, acc_waypoints=None):
+        """(t, p_act, v_act, a_act): the splines of the active joints, ``t`` an (N, 1) column (:82-156)."""
+        self._check(waypoints, vel_waypoints, acc_waypoints)
+        self.delta_t, self.T, self.N, t, k, u = spline_times(freq, time_points)
+        if np.size(time_points) != self.num_waypoints:
+            raise ValueError("%d time points for %d waypoints" % (np.size(time_points), self.num_waypoints))
+        coef = spline_coefficients(time_points, waypoints, vel_waypoints, acc_waypoints)
+        self.t = t.reshape(-1, 1)
+        self.q_act, self.dq_act, self.ddq_act = spline_samples(coef, k, u)
+        return self.t, self.q_act, self.dq_act, self.ddq_act
+
+    def get_full_config(self, freq, time_points, waypoints, vel_waypoints=None, acc_waypoints=None, device_resident=False):
+        """(t, p_full, v_full, a_full): the active joints' profiles in full configurations, ``robot.q0`` and zeros in the
+        other columns (:158-181).  ``device_resident``: p, v, a as ``GpuMatrix`` from ``figh_spline_sample``."""
+        if device_resident:
+            self._check(waypoints, vel_waypoints, acc_waypoints)
+            batch = spline_batch(self, freq, time_points, np.asarray(waypoints)[None], vel_waypoints, acc_waypoints)
+            self.delta_t, self.T, self.N, self.t = batch.delta_t, batch.T, batch.n_per, batch.t
+            return batch.t, batch.q, batch.v, batch.a
+        t, p_act, v_act, a_act = self.get_active_config(freq, time_points, waypoints, vel_waypoints, acc_waypoints)
+        self.q_full = np.array([self.robot.q0] * self.N)
+        self.dq_full = np.array([np.zeros_like(self.robot.v0)] * self.N)
+        self.ddq_full = np.array([np.zeros_like(self.robot.v0)] * self.N)
+        self.q_full[:, self.act_idxq] = p_act
+        self.dq_full[:, self.act_idxv] = v_act
+        self.ddq_full[:, self.act_idxv] = a_act
+        return t, self.q_full, self.dq_full, self.ddq_full
+
+    def check_cfg_constraints(self, q, v=None, tau=None, soft_lim=0):
+        """True when a position, velocity or effort limit of an active joint is violated at some sample (:183-233); prints
+        what the reference prints."""
+        m = self.rmodel
+        violated = False
+        for i in range(q.shape[0]):
+            for j in self.act_idxq:
+                delta_lim = soft_lim * abs(m.upperPositionLimit[j] - m.lowerPositionLimit[j])
+                if q[i, j] > m.upperPositionLimit[j] - delta_lim:
+                    print("Joint q %d upper limit violated!" % j)
+                    violated = True
+                elif q[i, j] < m.lowerPositionLimit[j] + delta_lim:
+                    print("Joint position idx_q %d lower limit violated!" % j)
+                    violated = True
+        for x, limit, text in ((v, m.velocityLimit, "Joint vel idx_v %d limits violated!"),
+                               (tau, m.effortLimit, "Joint effort idx_v %d limits violated!")):
+            if x is None:
+                continue
+            for i in range(x.shape[0]):
+                for j in self.act_idxv:
+                    if abs(x[i, j]) > (1 - soft_lim) * abs(limit[j]):
+                        print(text % j)
+                        violated = True
+        if not violated:
+            print("SUCCEEDED to generate waypoints for  a feasible initial cubic spline")
+        else:
+            print("FAILED to generate a feasible cubic spline")
+        return violated
+
+
+class TrajectoryBatch:
+    """B trajectories of n_per samples, resident: ``q`` (B n_per x nq), ``v``, ``a`` (B n_per x nv) as ``GpuMatrix`` with the
+    trajectories back to back -- what :func:`base_regressor_triangles_batch`, :func:`objective_cond_batch` and
+    :func:`calc_torque_batch` take in place of a list -- and the (n_per, 1) time column ``t`` they share."""
+
+    def __init__(self, B, n_per, q, v, a, t, delta_t=None, T=None):
+        self.B, self.n_per, self.q, self.v, self.a, self.t = int(B), int(n_per), q, v, a, t
+        self.delta_t, self.T = delta_t, T
+
+    def __len__(self):
+        return self.B
+
+    def numpy(self):
+        """``[(q_b, v_b, a_b), ...]`` on the host: the list form of the same arrays."""
+        q, v, a = (x.numpy().reshape(self.B, self.n_per, -1) for x in (self.q, self.v, self.a))
+        return [(q[b], v[b], a[b]) for b in range(self.B)]
+
+
+def waypoints_from_search_variables(X_batch, wp_init, n_wps, n_act):
+    """(B, n_act, n_wps) waypoint arrays from B rows of the optimiser's search variables: per row the ``reshape -> vstack ->
+    transpose`` of examples/tiago/optimal_trajectory.py:116-119."""
+    X = np.asarray(X_batch, dtype=np.float64)
+    X = X.reshape(-1, n_wps - 1, n_act)
+    first = np.broadcast_to(np.asarray(wp_init, dtype=np.float64).reshape(1, 1, n_act), (X.shape[0], 1, n_act))
+    return np.ascontiguousarray(np.concatenate((first, X), axis=1).transpose(0, 2, 1))
+
+
+def spline_batch(spline, freq, tps, wps_batch, vel_wps, acc_wps):
+    """B waypoint sets ``wps_batch`` (B, n_act, n_wps) -> :class:`TrajectoryBatch` in two launches (``figh_spline_sample``).
+    ``vel_wps`` / ``acc_wps``: (n_act, n_wps), one set for all trajectories as in the script, or (B, n_act, n_wps).  What
+    crosses the bus is the waypoints: B n_act n_wps doubles."""
+    from ..device import GpuMatrix
+    wps = np.ascontiguousarray(wps_batch, dtype=np.float64)
+    n_act, n_wps = spline.dim_q
+    if wps.ndim != 3 or wps.shape[1:] != (n_act, n_wps):
+        raise ValueError("wps_batch must be (B, %d, %d), got %r" % (n_act, n_wps, wps.shape))
+    B = wps.shape[0]
+    if vel_wps is None or acc_wps is None:
+        spline._check(wps[0], None, None)
+    strides, bufs, first = [], [], []
+    for x in (vel_wps, acc_wps):
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.shape not in ((n_act, n_wps), (B, n_act, n_wps)):
+            raise ValueError("velocity / acceleration waypoints must be (%d, %d) or (%d, %d, %d), got %r"
+                             % (n_act, n_wps, B, n_act, n_wps, x.shape))
+        strides.append(0 if x.ndim == 2 else n_act * n_wps)
+        first.append(x if x.ndim == 2 else x[0])
+        bufs.append(x.reshape(-1))
+    spline._check(wps[0], first[0], first[1])
+    delta_t, T, n_per, t, _, _ = spline_times(freq, tps)
+    if np.size(tps) != n_wps:
+        raise ValueError("%d time points for %d waypoints" % (np.size(tps), n_wps))
+    m = spline.rmodel
+    q, v, a = (GpuMatrix.empty(B * n_per, w) for w in (m.nq, m.nv, m.nv))
+    bufs = [_lib.DeviceArray.from_host(x) for x in bufs]
+    d_wps = _lib.DeviceArray.from_host(wps.reshape(-1))
+    d_q0 = _lib.DeviceArray.from_host(np.ascontiguousarray(spline.robot.q0, dtype=np.float64))
+    _lib.spline_sample(spline.robot.device_model(), B, n_wps, n_per, freq, spline.act_idxq, spline.act_idxv,
+                       np.asarray(tps, dtype=np.float64).reshape(-1), d_wps, bufs[0], strides[0], bufs[1], strides[1], d_q0,
+                       q.ptr, q.ld, v.ptr, a.ptr, v.ld)
+    return TrajectoryBatch(B, n_per, q, v, a, t.reshape(-1, 1), delta_t, T)
+
+
+def waypoint_sample_indices(t, tps):
+    """idx_waypoints of get_constraints_all_samples (:157-162): the samples whose time EQUALS one of ``tps[1:]``."""
+    t = np.asarray(t, dtype=np.float64).reshape(-1)
+    return np.flatnonzero(np.isin(t, np.asarray(tps, dtype=np.float64).reshape(-1)[1:]))
+
+
+def constraint_vector(spline, t_f, p_f, v_f, tau, tps):
+    """get_constraints_all_samples (examples/tiago/optimal_trajectory.py:156-174, :185-187) of one trajectory on host arrays,
+    without the collision distances: positions of the active joints at the waypoints, their velocities and efforts at every
+    sample, concatenated."""
+    Ns = len(p_f)
+    idx = waypoint_sample_indices(t_f, tps)
+    q_c = np.asarray(p_f)[idx, :][:, spline.act_idxq]
+    v_c = np.asarray(v_f)[:, spline.act_idxv]
+    tau = np.asarray(tau)
+    tau_c = np.zeros((Ns, len(spline.act_idxv)))
+    for k, j in enumerate(spline.act_idxv):
+        tau_c[:, k] = tau[j * Ns:(j + 1) * Ns]
+    return np.concatenate((q_c, v_c, tau_c), axis=None)
+
+
+def constraints_batch(spline, batch, tau, tps):
+    """(B, n_con) host array, row b = :func:`constraint_vector` of trajectory b, gathered on the device
+    (``figh_excitation_constraints``) and brought back in one copy.  ``tau``: what ``calc_torque_batch(robot, batch,
+    dict(param, device_resident=True))`` returns (the batched layout)."""
+    if not isinstance(tau, _lib.DeviceArray):
+        tau = _lib.DeviceArray.from_host(np.ascontiguousarray(tau, dtype=np.float64).reshape(-1))
+    nv = spline.rmodel.nv
+    if tau.size != nv * batch.B * batch.n_per:
+        raise ValueError("tau has %d entries, the batch has %d x %d samples of %d efforts" % (tau.size, batch.B, batch.n_per, nv))
+    idx = waypoint_sample_indices(batch.t, tps)
+    n_act = len(spline.act_idxv)
+    n_con = len(idx) * n_act + 2 * batch.n_per * n_act
+    out = _lib.DeviceArray((batch.B * n_con,), np.float64)
+    _lib.excitation_constraints(spline.robot.device_model(), batch.B, batch.n_per, spline.act_idxq, spline.act_idxv, idx,
+                                batch.q.ptr, batch.q.ld, batch.v.ptr, batch.v.ld, tau, out.ptr, n_con)
+    return out.to_host().reshape(batch.B, n_con)
+
+
+def evaluate_waypoints_batch(robot, spline, freq, tps, X_batch, vel_wps, acc_wps, wp_init, param, idx_e, idx_base,
+                             R_stack=None):
+    """``(conds, constraints)``: ``objective`` and ``constraints`` of the script's Ipopt problem
+    (examples/tiago/optimal_trajectory.py:100-188, :296-327) at the B rows of ``X_batch`` -- the points of one finite-difference
+    gradient or Jacobian.  Waypoints go up, B condition numbers (through B r x r triangles) and the (B, n_con) constraint
+    vectors come back; the samples, v and tau never leave the device."""
+    n_act, n_wps = spline.dim_q
+    wps = waypoints_from_search_variables(X_batch, wp_init, n_wps, n_act)
+    batch = spline_batch(spline, freq, tps, wps, vel_wps, acc_wps)
+    conds = objective_cond_batch(robot, batch, param, idx_e, idx_base, R_stack)
+    d_tau = calc_torque_batch(robot, batch, dict(param, device_resident=True))
+    return conds, constraints_batch(spline, batch, d_tau, tps)

@@ -91,7 +91,7 @@ typedef struct figh_model_s *figh_model_t;
  * (round 5 did so for figh_tsqr_selected_wrench / figh_regressor_build_padded without a bump: a library of the older ABI
  * accepts the longer argument list under cdecl and silently ignores the new arguments).  figaroh_plus_amd/_lib.py refuses a
  * library -- in-tree or FIGH_LIB_PATH -- whose figh_version() differs from the value it was written against. */
-#define FIGH_ABI_VERSION 109
+#define FIGH_ABI_VERSION 110
 int figh_version(void);
 const char *figh_last_error(void);
 int figh_device_count(int *count);
@@ -468,6 +468,50 @@ int figh_joint_difference(figh_model_t model, int64_t N, const double *d_q, doub
  * doubles. */
 int figh_gradient_cols(const double *d_F, int64_t rows, int cols, int64_t ld, int ncols_active, double h, const double *d_h,
                        double *d_G, int64_t ldg);
+
+/* ------------------------------------------------------------------ excitation trajectories
+ * The front and the back of the excitation loop: waypoints in, resident (q, v, a) out, constraint vectors out; in between
+ * figh_regressor_tsqr_batch[_fused] and figh_regressor_apply read the same buffers, so no sample array crosses the bus.
+ * The translation unit is compiled without FMA contraction; its header states the operation order.
+ *
+ * figh_spline_sample: CubicSpline.get_full_config (examples/tiago/utils/cubic_spline.py:82-181) with velocity and
+ * acceleration waypoints, for B waypoint sets at once: between neighbouring waypoints the unique quintic through position,
+ * velocity and acceleration at both ends (what ndcurves.exact_cubic builds from two waypoints and
+ * init_vel / end_vel / init_acc / end_acc, :110-122 -- the same polynomial, not the same bits), sampled at
+ * t_i = h_tps[0] + i * delta_t, delta_t = 1 / freq, i < n_per (:133-153; the reference's N is
+ * int((tps[-1] - tps[0]) / delta_t) + 1, a division by the rounded delta_t), and scattered
+ * into full configurations (:171-178): trajectory b fills rows [b n_per, (b + 1) n_per) of d_q (B n_per x nq, ldq), d_v and
+ * d_a (B n_per x nv, ldv) -- the layout figh_regressor_tsqr_batch[_fused] and figh_regressor_apply read.  h_act_idxq /
+ * h_act_idxv: the n_act active joints' idx_q / idx_v.  h_tps: n_wps >= 2 strictly increasing time points shared by the batch.
+ * d_wps: B x n_act x n_wps (the reference's (n_act, n_wps) array per trajectory); d_vel_wps / d_acc_wps: the same layout,
+ * trajectory b at offset b * vel_stride / b * acc_stride (0: one set for all trajectories).  d_q0: nq doubles, robot.q0, the
+ * fill of the position columns no active joint owns; such columns of d_v / d_a are written as +0.0.  Nothing is written
+ * outside the B n_per x width part of a padded buffer.  The segment of t_i is the largest k with h_tps[k] <= t_i, at most
+ * n_wps - 2, and the local time is min(t_i - h_tps[k], h_tps[k+1] - h_tps[k]): where rounding puts the last sample behind
+ * h_tps[n_wps - 1] ndcurves raises, this entry evaluates the end of the last segment.  Two launches whatever B is (segment
+ * coefficients into a workspace table, then one thread per output element); bit-equal to the package's NumPy mirror.
+ * FIGH_ERR_INVALID: time points not strictly increasing, a stride between 1 and n_act n_wps - 1, n_per max(nq, nv) >= 2^31
+ * (a trajectory is indexed in 32 bits; B is not limited), an index pair that is no
+ * joint.  FIGH_ERR_UNSUPPORTED (nothing launched, figh_last_error says why): an active joint that is not one revolute or
+ * prismatic degree of freedom; inactive joints may be anything.  Without a HIP device: FIGH_ERR_NO_DEVICE, before any
+ * argument is looked at. */
+int figh_spline_sample(figh_model_t model, int64_t B, int n_wps, int n_act, int64_t n_per, double freq,
+                       const int32_t *h_act_idxq, const int32_t *h_act_idxv, const double *h_tps, const double *d_wps,
+                       const double *d_vel_wps, int64_t vel_stride, const double *d_acc_wps, int64_t acc_stride,
+                       const double *d_q0, double *d_q, int64_t ldq, double *d_v, double *d_a, int64_t ldv);
+/* figh_excitation_constraints: the constraint vector of get_constraints_all_samples
+ * (examples/tiago/optimal_trajectory.py:156-174, :185-187) without the collision distances, for B trajectories: row b of d_out
+ * (B x n_con, ld_out; n_con = n_idx n_act + 2 n_per n_act) is np.concatenate((q_wp, v_act, tau_act), axis=None) with
+ * q_wp = p_f[idx_waypoints][:, act_idxq] (n_idx x n_act), v_act = v_f[:, act_idxv] (n_per x n_act) and tau_act[i, k] =
+ * tau[act_idxv[k] * n_per + i].  d_q / d_v: the batched samples as figh_spline_sample leaves them; d_tau: the batched layout
+ * of figh_regressor_apply over all B n_per samples (row j B n_per + b n_per + i).  h_idx_waypoints: n_idx sample indices in
+ * [0, n_per), found by the host (the reference compares t_f[i] with tps[1:] for exact equality).  Pure copies; n_con < 2^31.
+ * The active
+ * joints are checked as in figh_spline_sample; without a HIP device: FIGH_ERR_NO_DEVICE, before any argument is looked at. */
+int figh_excitation_constraints(figh_model_t model, int64_t B, int64_t n_per, int n_act, const int32_t *h_act_idxq,
+                                const int32_t *h_act_idxv, int n_idx, const int32_t *h_idx_waypoints, const double *d_q,
+                                int64_t ldq, const double *d_v, int64_t ldv, const double *d_tau, double *d_out,
+                                int64_t ld_out);
 
 /* ------------------------------------------------------------------ multi-GPU (RCCL over xGMI), SURVEY.md section 8e
  * One process per GPU.  Rank 0 calls figh_comm_unique_id and ships the 128 bytes to the other ranks by any
