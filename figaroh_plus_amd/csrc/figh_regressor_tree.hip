@@ -1014,10 +1014,13 @@ int launch_regressor_tree(const figh_model_s *m, int mode, int flags, int ft_mas
                                    ls};
     auto it = g_tapes.find(key);
     if (it == g_tapes.end()) {
+        // figh_model_set_active_rows restricts what figh_regressor_build_padded stores (ls == 16); figh_regressor_build (the
+        // reference's layout, ls == 14) ignores the setting and writes every row block (figh.h)
+        const unsigned long long active = ls == 16 ? m->active_rows : ~0ull;
         std::vector<TapeOp> ops = extff ? build_tape_extff(h, flags, ft_mask, ls, nlive >= 0 ? link_pos : nullptr, fc)
                                         : (mode == FIGH_MODE_JOINT_TORQUE && h.nv == h.njoints - 1
-                                               ? build_tape_torque_rows(h, flags, ls, m->active_rows)
-                                               : build_tape_rows(h, mode, flags, ft_mask, ls, m->active_rows));
+                                               ? build_tape_torque_rows(h, flags, ls, active)
+                                               : build_tape_rows(h, mode, flags, ft_mask, ls, active));
         DeviceTape dt;
         dt.n = (int)ops.size();
         dt.extff = extff;

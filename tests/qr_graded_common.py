@@ -14,6 +14,8 @@ INT_MAX = 2 ** 10
 # residuals of test_reductions_graded.py, formed from R, share it): measured 5.2e-15 on an MI355X (rfactor 20011 x 511,
 # wide profile; 7.7e-15 with dependent columns)
 TOL_BACKWARD = 1e-13
+# power-of-two column-scale ranges (lo, hi) of the graded inputs: TIAGo's kept columns span 7e4 in norm; "wide" is 2^60
+PROFILES = {"tiago": (-10, 7), "wide": (-30, 30)}
 
 
 def int_matrix(rng, rows, n, lo=-INT_MAX, hi=INT_MAX):
@@ -36,6 +38,18 @@ def small_positions(n, edges=(16, 64, 80, 192, 256, 320, 336, 384, 400)):
     for e in edges:
         pos.update((e - 1, e))
     return sorted(p for p in pos if 0 <= p < n)
+
+
+def graded_triangles(rng, count, nc, profile):
+    """count integer upper triangles, diagonally weighted (|diag| in [512, 1024], small off-diagonal entries) so that the
+    stack stays well conditioned after equilibration, graded by power-of-two column scales."""
+    B = max(1, 1024 // (4 * int(np.ceil(np.sqrt(nc)))))
+    T = rng.integers(-B, B + 1, (count, nc, nc)).astype(np.float64)
+    i = np.arange(nc)
+    T[:, i, i] = rng.integers(512, 1025, (count, nc)) * rng.choice([-1.0, 1.0], (count, nc))
+    T = np.triu(T)
+    lo, hi = PROFILES[profile]
+    return T, graded_scales(rng, nc, lo, hi, small_positions(nc) + [nc // 2])
 
 
 def exact_gram(M, s=None, row_exp=None):

@@ -29,7 +29,7 @@ TOL_BACKWARD = qg.TOL_BACKWARD  # measured 5.2e-15 (rfactor 20011 x 511, wide pr
 C_FORWARD = 200.0     # forward <= C_FORWARD cond u: measured 17.6 cond u (rfactor 20011 x 511, wide)
 C_DIAG = 200.0        # diagonal <= C_DIAG cond u: measured 17.3 cond u (same case)
 
-PROFILES = {"tiago": (-10, 7), "wide": (-30, 30)}
+PROFILES = qg.PROFILES
 NS = [1, 15, 16, 17, 49, 63, 64, 65, 79, 80, 81, 96, 97, 193, 272, 321, 336, 385, 400, 511]
 
 
@@ -124,16 +124,7 @@ def test_rfactor_graded_48_row_form(lib, record_property):
         _check(R, G, record_property, "rfactor_48_row_form")
 
 
-def _graded_triangles(rng, count, nc, profile):
-    """count integer upper triangles, diagonally weighted (|diag| in [512, 1024], small off-diagonal entries) so that the
-    stack stays well conditioned after equilibration, graded by power-of-two column scales."""
-    B = max(1, 1024 // (4 * int(np.ceil(np.sqrt(nc)))))
-    T = rng.integers(-B, B + 1, (count, nc, nc)).astype(np.float64)
-    i = np.arange(nc)
-    T[:, i, i] = rng.integers(512, 1025, (count, nc)) * rng.choice([-1.0, 1.0], (count, nc))
-    T = np.triu(T)
-    lo, hi = PROFILES[profile]
-    return T, qg.graded_scales(rng, nc, lo, hi, qg.small_positions(nc) + [nc // 2])
+_graded_triangles = qg.graded_triangles  # (importable without pytest: the call-sequence worker builds the same stacks)
 
 
 MERGE_CASES = [(1, 5), (17, 40), (50, 2), (50, 16), (50, 300), (50, 2039), (64, 700), (65, 9), (80, 130), (49, 4500), (81, 2),
