@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # FIGH_LIB_PATH: another build of the same ABI (same-box A/B of kernel variants); default is the in-tree library
 LIB_PATH = os.environ.get("FIGH_LIB_PATH") or os.path.join(_HERE, "libfigh.so")
 
-ABI_VERSION = 110  # include/figh.h FIGH_ABI_VERSION: load() refuses a library of another ABI
+ABI_VERSION = 111  # include/figh.h FIGH_ABI_VERSION: load() refuses a library of another ABI
 
 FIGH_OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_ALLOC, ERR_UNSUPPORTED, ERR_COMM = -1, -2, -3, -4, -5
@@ -122,6 +122,13 @@ SIGNATURES = {
     "figh_excitation_constraints": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, _c_int32_p, _c_int32_p, C.c_int,
                                               _c_int32_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                               C.c_void_p, C.c_int64]),
+    "figh_kinematic_regressor": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, _c_double_p, C.c_int,
+                                           _c_double_p, _c_int32_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
+                                           C.c_int64, C.c_void_p, C.c_void_p]),
+    "figh_calib_fkm_batch": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int, _c_int32_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, _c_double_p, C.c_int, _c_double_p,
+                                       C.c_int, C.c_void_p, C.c_int64]),
+    "figh_gather_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
     "figh_comm_available": (C.c_int, []),
     "figh_comm_unique_id": (C.c_int, [C.c_void_p]),
     "figh_comm_init": (C.c_int, [C.c_int, C.c_int, C.c_void_p]),
@@ -543,6 +550,49 @@ def excitation_constraints(model, B, n_per, act_idxq, act_idxv, idx_waypoints, q
     check(load().figh_excitation_constraints(model.handle, B, n_per, len(iq), iq.ctypes.data_as(_c_int32_p),
                                              iv.ctypes.data_as(_c_int32_p), len(iw), iw.ctypes.data_as(_c_int32_p), q_ptr, ldq,
                                              v_ptr, ldv, d_tau.ptr, out_ptr, ld_out))
+
+
+def _ptr(x):
+    return x.ptr if hasattr(x, "ptr") else x
+
+
+def kinematic_regressor(model, N, q_ptr, ldq, end_joint, end_placement, start_joint, start_placement, support, meas_mask,
+                        R_ptr, ldr, J_ptr, ldj, rowsq_R_ptr=None, rowsq_J_ptr=None):
+    """figh_kinematic_regressor on raw device addresses: the measured row blocks of the kinematic regressor R and / or of
+    the frame Jacobian J (either may be None), and their rows' sums of squares.  Placements are 12 doubles (R, p)."""
+    ep = _f64(end_placement).reshape(-1)
+    sp = _f64(start_placement).reshape(-1) if start_placement is not None else None
+    sup = _i32(support).reshape(-1)
+    if ep.size != 12 or (sp is not None and sp.size != 12):
+        raise ValueError("kinematic_regressor: a placement is 12 doubles (rotation row-major, translation)")
+    check(load().figh_kinematic_regressor(model.handle, N, _ptr(q_ptr), ldq, int(end_joint), ep.ctypes.data_as(_c_double_p),
+                                          int(start_joint), sp.ctypes.data_as(_c_double_p) if sp is not None else None,
+                                          sup.ctypes.data_as(_c_int32_p), len(sup), int(meas_mask), _ptr(R_ptr), ldr,
+                                          _ptr(J_ptr), ldj, _ptr(rowsq_R_ptr), _ptr(rowsq_J_ptr)))
+
+
+def calib_fkm_batch(model, B, N, q_ptr, ldq, chain, d_placements, d_wMo, d_eeMf, end_joint, end_placement, start_joint,
+                    start_placement, meas_mask, out_ptr, ld_out):
+    """figh_calib_fkm_batch: the measured pose components of B parameter vectors x N poses, out[b ld_out + k N + i]."""
+    ep = _f64(end_placement).reshape(-1)
+    sp = _f64(start_placement).reshape(-1) if start_placement is not None else None
+    ch = _i32(chain).reshape(-1)
+    if ep.size != 12 or (sp is not None and sp.size != 12):
+        raise ValueError("calib_fkm_batch: a placement is 12 doubles (rotation row-major, translation)")
+    if d_placements.size < B * len(ch) * 12 or d_wMo.size < 12 * B or d_eeMf.size < 12 * B:
+        raise ValueError("calib_fkm_batch: placements / wMo / eeMf hold fewer than B x n_chain x 12 / B x 12 doubles")
+    check(load().figh_calib_fkm_batch(model.handle, B, N, _ptr(q_ptr), ldq, len(ch), ch.ctypes.data_as(_c_int32_p),
+                                      d_placements.ptr, d_wMo.ptr, d_eeMf.ptr, int(end_joint),
+                                      ep.ctypes.data_as(_c_double_p), int(start_joint),
+                                      sp.ctypes.data_as(_c_double_p) if sp is not None else None, int(meas_mask),
+                                      _ptr(out_ptr), ld_out))
+
+
+def gather_rows(W_ptr, ldw, cols, d_idx, n, out_ptr, ld_out):
+    """figh_gather_rows: out[r, :] = W[idx[r], :], order kept (d_idx: int32 DeviceArray of at least n entries)."""
+    if d_idx.size < n:
+        raise ValueError("gather_rows: %d indices for n = %d" % (d_idx.size, n))
+    check(load().figh_gather_rows(_ptr(W_ptr), ldw, cols, d_idx.ptr, n, _ptr(out_ptr), ld_out))
 
 
 def compact_rows(W_ptr, rows, cols, ldw, tau_ptr, key_col, threshold, Wout_ptr, ld_out, tauout_ptr):

@@ -120,6 +120,7 @@ enum WorkspaceSlot {
     kWsDynamicsState,       // figh_regressor_apply (tree kernel): per-wave link wrenches and transforms
     kWsSplineTable,         // figh_spline_sample: segment coefficients, local times, time points, segment indices
     kWsConstraintIdx,       // figh_excitation_constraints: the waypoint sample indices
+    kWsKinematicJacobian,   // figh_kinematic_regressor: J of two frames when only its rows' sums of squares are asked for
     kWorkspaceSlots
 };
 

@@ -155,11 +155,23 @@ class JointModel:
         return "JointModel" + {JT_REVOLUTE: "R", JT_PRISMATIC: "P", JT_CONTINUOUS: "RUB"}[self.jtype] + letter
 
 
+class Frame:
+    """Operational frame: a placement fixed to joint ``parent`` (Pinocchio's ``model.frames[k]``).  The flat models
+    carry no link frames, so frame IDS differ from Pinocchio's for the same URDF; frame NAMES are the interface."""
+
+    __slots__ = ("name", "parent", "placement")
+
+    def __init__(self, name, parent, placement=None):
+        self.name, self.parent = name, int(parent)
+        self.placement = SE3() if placement is None else placement.copy()
+
+
 class Data:
     """Placeholder for Pinocchio's scratch ``Data``; the HIP path keeps no host scratch."""
 
     def __init__(self, model):
         self.oMi = [SE3() for _ in range(model.njoints)]
+        self.oMf = [SE3() for _ in range(len(model.frames))]
 
 
 class Model:
@@ -170,6 +182,7 @@ class Model:
         self.jointPlacements = [SE3()]
         self.inertias = _InertiaVector([Inertia()])
         self.joints = [JointModel(0, JT_UNIVERSE, np.zeros(3), 0, 0)]
+        self.frames = [Frame("universe", 0)]
         self.gravity = np.array([0.0, 0.0, -9.81])
         self.nq = 0
         self.nv = 0
@@ -192,6 +205,7 @@ class Model:
         self.jointPlacements.append(placement.copy())
         self.inertias.append(Inertia())
         self.joints.append(JointModel(jid, jtype, axis, self.nq, self.nv))
+        self.frames.append(Frame(name, jid))
         nq, nv = _NQ[jtype], _NV[jtype]
         lo, up, vel, eff = limits if limits is not None else (-math.inf, math.inf, math.inf, math.inf)
         if jtype == JT_CONTINUOUS:
@@ -225,6 +239,31 @@ class Model:
 
     def existJointName(self, name):
         return name in self.names
+
+    def addFrame(self, name, parent_joint, placement=None):
+        """Tool or marker frame fixed to joint ``parent_joint``; returns its frame id."""
+        if not 0 <= int(parent_joint) < self.njoints:
+            raise ValueError("addFrame: joint %r is not in the model" % (parent_joint,))
+        self.frames.append(Frame(name, parent_joint, placement))
+        return len(self.frames) - 1
+
+    def getFrameId(self, name):
+        """Index of the first frame called ``name``; ``len(frames)`` when there is none (as Pinocchio answers)."""
+        for k, f in enumerate(self.frames):
+            if f.name == name:
+                return k
+        return len(self.frames)
+
+    @property
+    def supports(self):
+        """supports[j]: the joint ids from 0 to j along the tree (Pinocchio's ``model.supports``)."""
+        out = []
+        for j in range(self.njoints):
+            path = [j]
+            while path[-1] > 0:
+                path.append(self.parents[path[-1]])
+            out.append(np.array(path[::-1], dtype=np.int64))
+        return out
 
     def createData(self):
         return Data(self)
@@ -314,6 +353,7 @@ class Model:
             m.inertias.append(Inertia())
             m.joints.append(JointModel(i, int(flat["jtype"][i]), axis[i],
                                        int(flat["idx_q"][i]), int(flat["idx_v"][i])))
+            m.frames.append(Frame(flat["names"][i], i))
         mass, lever, inertia = dec(flat["mass"]), dec(flat["lever"]).reshape(n, 3), dec(flat["inertia"]).reshape(n, 9)
         for i in range(n):
             m.inertias[i] = Inertia(mass[i], lever[i], inertia[i].reshape(3, 3))
@@ -321,6 +361,10 @@ class Model:
         m._lower, m._upper = list(dec(flat["lower"])), list(dec(flat["upper"]))
         m._vel, m._eff = list(dec(flat["velocity"])), list(dec(flat["effort"]))
         m._sync_limits()
+        # optional tool / marker frames: [{"name": ..., "parent": joint id, "placement": 12 doubles (R row-major, p)}, ...]
+        for fr in flat.get("frames", ()):
+            P = np.array([float(x) for x in fr["placement"]], dtype=float)
+            m.addFrame(fr["name"], int(fr["parent"]), SE3(P[:9].reshape(3, 3), P[9:]))
         return m
 
 

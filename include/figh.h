@@ -91,7 +91,7 @@ typedef struct figh_model_s *figh_model_t;
  * (round 5 did so for figh_tsqr_selected_wrench / figh_regressor_build_padded without a bump: a library of the older ABI
  * accepts the longer argument list under cdecl and silently ignores the new arguments).  figaroh_plus_amd/_lib.py refuses a
  * library -- in-tree or FIGH_LIB_PATH -- whose figh_version() differs from the value it was written against. */
-#define FIGH_ABI_VERSION 110
+#define FIGH_ABI_VERSION 111
 int figh_version(void);
 const char *figh_last_error(void);
 int figh_device_count(int *count);
@@ -512,6 +512,57 @@ int figh_excitation_constraints(figh_model_t model, int64_t B, int64_t n_per, in
                                 const int32_t *h_act_idxv, int n_idx, const int32_t *h_idx_waypoints, const double *d_q,
                                 int64_t ldq, const double *d_v, int64_t ldv, const double *d_tau, double *d_out,
                                 int64_t ld_out);
+
+/* ------------------------------------------------------------------ geometric calibration
+ * The kinematic regressor and the updated forward kinematics of src/figaroh/calibration/calibration_tools.py, over
+ * independent configurations, one per lane.  Conventions: 6-vectors are (linear, angular); a placement
+ * (12 doubles: R row-major, then p) maps child to parent coordinates; Ad(M) = [[R, skew(p) R], [0, R]];
+ * A_j = oM_parent(j) . jointPlacement_j, oM_j = A_j . M_j(q_j), and a frame on joint j with placement P is oMf = oM_j . P.
+ * d_q: N x nq configurations, leading dimension ldq.  meas_mask: bit c set <=> component c of (x y z roll pitch yaw) is
+ * measured (param["measurability"]); n_meas is the number of set bits.
+ *
+ * figh_kinematic_regressor: the loop body of calculate_identifiable_kinematics_model (:1432-1450) for all samples --
+ * pin.computeFrameKinematicRegressor(..., LOCAL) and pin.computeFrameJacobian(..., LOCAL) of calculate_kinematics_model
+ * (:1387-1391) when start_joint = -1 (universe), get_rel_kinreg (:693-704) and get_rel_jac (:729-739) otherwise.  The end
+ * frame sits on end_joint with h_end_placement, the start frame on start_joint with h_start_placement.
+ * d_R (n_meas N x 6 (njoints - 1), ldr): row k N + i is row c_k of sample i, c_k the k-th measured component (the
+ * reference's rows N c + i of the unmeasured c are zero and deleted at :1452-1456); columns [6 (p - 1), 6 p) hold
+ * Ad(oMf^-1 . A_p) for the n_support joints p of h_support (the whole root -> end path for calculate_kinematics_model,
+ * get_sup_joints' list otherwise), each of which must lie between the root and the end frame or between the root and the
+ * start frame.  d_J (n_meas N x nv, ldj): the columns of joint j on the root -> end path are Ad(oMf^-1 . oM_j) . S_j, minus,
+ * with a start frame, the same for the start frame in ITS local frame (J_end - J_start, :737-739); S is (0, axis) for
+ * revolute and continuous joints, (axis, 0) for prismatic ones, I6 for a free-flyer.  All other columns are +0.0, written
+ * by one memset of the n_meas N x width part of each matrix ahead of the launches; nothing is written outside that part
+ * of a padded buffer.  d_rowsq_R / d_rowsq_J (n_meas N doubles): the rows' sums of squares, for the norm < 1e-6 deletion of
+ * :1452-1461.  Each of d_R, d_J, d_rowsq_R, d_rowsq_J may be NULL on its own (sums without their matrix: the same walk,
+ * nothing stored; for J between two frames through a workspace).  Unlike the reference, nv need not equal njoints - 1.  No atomics: two calls give the
+ * same bits.  FIGH_ERR_INVALID (nothing launched, figh_last_error says why): an end or start joint off the model, a
+ * support joint off both paths or listed twice, meas_mask outside [1, 63], a leading dimension below the width.  Without a
+ * HIP device: FIGH_ERR_NO_DEVICE, before any argument is looked at. */
+int figh_kinematic_regressor(figh_model_t model, int64_t N, const double *d_q, int64_t ldq, int end_joint,
+                             const double *h_end_placement, int start_joint, const double *h_start_placement,
+                             const int32_t *h_support, int n_support, int meas_mask, double *d_R, int64_t ldr, double *d_J,
+                             int64_t ldj, double *d_rowsq_R, double *d_rowsq_J);
+/* figh_calib_fkm_batch: the loop over the poses of calc_updated_fkm (:1290-1311) for B parameter vectors in one launch (the
+ * B = nvar + 1 vectors of a forward-difference Levenberg-Marquardt Jacobian).  h_chain: the n_chain joints whose placements
+ * the parameters update (param["actJoint_idx"]); d_placements (B x n_chain x 12): their updated placements
+ * (update_joint_placement, :1352-1361, formed by the host in float64); d_wMo / d_eeMf (B x 12): the base and marker
+ * transforms (:1214-1251).  Per vector b and pose i: oMee = oM_start^-1 . oM_end with the updated placements
+ * (get_rel_transform, :613-617; formed from the last joint both branches share, below which the factors cancel),
+ * wMf = wMo[b] . oMee . eeMf[b] (:1300-1301), and the measured components of (translation, matrixToRpy(rotation)) --
+ * pitch = atan2(-R20, sqrt(R00^2 + R10^2)), yaw = atan2(R10, R00), roll = atan2(R21, R22) -- go to
+ * d_out[b ld_out + k N + i] (PEE.flatten("C"), :1311-1314).  ld_out >= n_meas N.  start_joint = -1: universe.  B is not
+ * limited.  FIGH_ERR_INVALID as for figh_kinematic_regressor, and for a chain joint off the model or listed twice; without
+ * a HIP device: FIGH_ERR_NO_DEVICE, before any argument is looked at. */
+int figh_calib_fkm_batch(figh_model_t model, int64_t B, int64_t N, const double *d_q, int64_t ldq, int n_chain,
+                         const int32_t *h_chain, const double *d_placements, const double *d_wMo, const double *d_eeMf,
+                         int end_joint, const double *h_end_placement, int start_joint, const double *h_start_placement,
+                         int meas_mask, double *d_out, int64_t ld_out);
+/* figh_gather_rows: d_out[r, :] = d_W[d_row_idx[r], :] for r < n, cols columns -- np.delete(R, zero_rows, axis=0) (:1456,
+ * :1461) with the kept rows listed in order by the caller, who reads the row sums of squares.  Pure copies; n = 0 does
+ * nothing.  FIGH_ERR_INVALID: a leading dimension below cols; the indices are not checked. */
+int figh_gather_rows(const double *d_W, int64_t ldw, int cols, const int32_t *d_row_idx, int64_t n, double *d_out,
+                     int64_t ld_out);
 
 /* ------------------------------------------------------------------ multi-GPU (RCCL over xGMI), SURVEY.md section 8e
  * One process per GPU.  Rank 0 calls figh_comm_unique_id and ships the 128 bytes to the other ranks by any
