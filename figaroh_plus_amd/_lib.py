@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # FIGH_LIB_PATH: another build of the same ABI (same-box A/B of kernel variants); default is the in-tree library
 LIB_PATH = os.environ.get("FIGH_LIB_PATH") or os.path.join(_HERE, "libfigh.so")
 
-ABI_VERSION = 111  # include/figh.h FIGH_ABI_VERSION: load() refuses a library of another ABI
+ABI_VERSION = 112  # include/figh.h FIGH_ABI_VERSION: load() refuses a library of another ABI
 
 FIGH_OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_ALLOC, ERR_UNSUPPORTED, ERR_COMM = -1, -2, -3, -4, -5
@@ -129,6 +129,9 @@ SIGNATURES = {
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, _c_double_p, C.c_int, _c_double_p,
                                        C.c_int, C.c_void_p, C.c_int64]),
     "figh_gather_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
+    "figh_design_gram": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, _c_double_p]),
+    "figh_design_scores": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, _c_double_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
     "figh_comm_available": (C.c_int, []),
     "figh_comm_unique_id": (C.c_int, [C.c_void_p]),
     "figh_comm_init": (C.c_int, [C.c_int, C.c_int, C.c_void_p]),
@@ -593,6 +596,24 @@ def gather_rows(W_ptr, ldw, cols, d_idx, n, out_ptr, ld_out):
     if d_idx.size < n:
         raise ValueError("gather_rows: %d indices for n = %d" % (d_idx.size, n))
     check(load().figh_gather_rows(_ptr(W_ptr), ldw, cols, d_idx.ptr, n, _ptr(out_ptr), ld_out))
+
+
+def design_gram(R_ptr, ldr, N, c, n, w_ptr=None):
+    """figh_design_gram: M = sum_i w_i sum_k r_{k,i} r_{k,i}^T over the resident pool, as an (n, n) host array (w_ptr: N
+    device doubles, None = all ones)."""
+    M = np.empty((max(int(n), 0), max(int(n), 0)))
+    check(load().figh_design_gram(_ptr(R_ptr), ldr, N, c, n, _ptr(w_ptr), M.ctypes.data_as(_c_double_p)))
+    return M
+
+
+def design_scores(R_ptr, ldr, N, c, n, L, trace_ptr, det_add_ptr, det_rm_ptr):
+    """figh_design_scores: tr G_i, det(I + G_i), det(I - G_i) of G_i = R_i M^-1 R_i^T for every candidate, from the host
+    Cholesky factor L of M (n x n, lower triangle read); each output (N device doubles) may be None, not all three."""
+    L = _f64(L)
+    if L.shape != (n, n):
+        raise ValueError("design_scores: L is %r, expected (%d, %d)" % (L.shape, n, n))
+    check(load().figh_design_scores(_ptr(R_ptr), ldr, N, c, n, L.ctypes.data_as(_c_double_p), _ptr(trace_ptr),
+                                    _ptr(det_add_ptr), _ptr(det_rm_ptr)))
 
 
 def compact_rows(W_ptr, rows, cols, ldw, tau_ptr, key_col, threshold, Wout_ptr, ld_out, tauout_ptr):

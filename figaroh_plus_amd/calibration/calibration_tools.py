@@ -15,7 +15,7 @@ Levenberg-Marquardt cost, and the base-parameter reduction of ``src/figaroh/cali
   ``get_joint_offset`` (``:252-298``) are mirrored because the base-parameter names are built from them.
 
 Out of scope: data loading, several markers, the elastic ``non_geom`` terms of
-``update_forward_kinematics[_2]``, posture selection and the Levenberg-Marquardt driver itself.
+``update_forward_kinematics[_2]`` and the Levenberg-Marquardt driver itself; posture selection is ``optimal_design``.
 """
 import math
 

@@ -121,6 +121,9 @@ enum WorkspaceSlot {
     kWsSplineTable,         // figh_spline_sample: segment coefficients, local times, time points, segment indices
     kWsConstraintIdx,       // figh_excitation_constraints: the waypoint sample indices
     kWsKinematicJacobian,   // figh_kinematic_regressor: J of two frames when only its rows' sums of squares are asked for
+    kWsDesignPartials,      // figh_design_gram: the workgroups' tile partials
+    kWsDesignGram,          // figh_design_gram: M ahead of its copy to the host
+    kWsDesignFactor,        // figh_design_scores: the packed, padded Cholesky factor
     kWorkspaceSlots
 };
 

@@ -91,7 +91,7 @@ typedef struct figh_model_s *figh_model_t;
  * (round 5 did so for figh_tsqr_selected_wrench / figh_regressor_build_padded without a bump: a library of the older ABI
  * accepts the longer argument list under cdecl and silently ignores the new arguments).  figaroh_plus_amd/_lib.py refuses a
  * library -- in-tree or FIGH_LIB_PATH -- whose figh_version() differs from the value it was written against. */
-#define FIGH_ABI_VERSION 111
+#define FIGH_ABI_VERSION 112
 int figh_version(void);
 const char *figh_last_error(void);
 int figh_device_count(int *count);
@@ -563,6 +563,36 @@ int figh_calib_fkm_batch(figh_model_t model, int64_t B, int64_t N, const double 
  * nothing.  FIGH_ERR_INVALID: a leading dimension below cols; the indices are not checked. */
 int figh_gather_rows(const double *d_W, int64_t ldw, int cols, const int32_t *d_row_idx, int64_t n, double *d_out,
                      int64_t ld_out);
+
+/* ------------------------------------------------------------------ D-optimal posture selection
+ * The two passes behind examples/tiago/optimal_config.py and examples/ur10/optimal_config.py over a resident pool of
+ * candidate postures.  d_R: the base kinematic regressor as calculate_base_kinematics_regressor leaves it, row-major with
+ * leading dimension ldr >= n: row k N + i is measured component k < c (c = param["calibration_index"], 1 .. 6) of candidate
+ * i < N, n columns (1 .. FIGH_DESIGN_MAX_COLS).  rearrange_rb (:31-39) is not needed and no X_i = R_i^T R_i of
+ * sub_info_matrix (:42-60) is stored.  Addresses are formed in 64 bits (c N ldr may exceed 2^31).
+ *
+ * figh_design_gram: h_M (n x n, row-major, HOST) = sum_i d_w[i] sum_k r_{k,i} r_{k,i}^T, the Mw of SOCP.add_constraints
+ * (:137-140); d_w = NULL: all ones (M_whole of calculate_detroot_whole, :262).  fp64 on the matrix pipe, both triangles
+ * written and exactly symmetric, per-workgroup partials through the library's workspace summed in a fixed order: no
+ * atomics, two calls give the same bits whatever ldr.  A candidate with d_w[i] = 0 contributes exact zeros.  The call
+ * returns when h_M is written.
+ *
+ * figh_design_scores: h_L (n x n row-major, HOST, lower triangle read) is the Cholesky factor of M.  With
+ * G_i = R_i M^-1 R_i^T (c x c):  d_trace[i] = tr G_i (the variance function of the design: max_i <= n (1 + eps) certifies
+ * D-efficiency >= 1 / (1 + eps));  d_det_add[i] = det(I + G_i) = det(M + X_i) / det M, the score of Detmax's add scan
+ * (:98-104);  d_det_rm[i] = det(I - G_i) = det(M - X_i) / det M, the score of its remove scan (:112-119), +0.0 as soon as
+ * a pivot is not positive (M - X_i is not positive definite).  Each output is N doubles and may be NULL on its own, not all
+ * three; nothing is written outside the N entries.  The operation order is fixed in the header comment of
+ * csrc/figh_design.hip and compiled without FMA contraction: the results are bit-equal to the NumPy mirror
+ * (calibration/optimal_design.py).
+ *
+ * Both: FIGH_ERR_INVALID (nothing launched, figh_last_error says why) for c or n out of range, ldr < n, N < 1, a NULL
+ * d_R / h_M / h_L, a diagonal entry of L that is not finite and positive, all outputs NULL.  Without a HIP device:
+ * FIGH_ERR_NO_DEVICE, before any argument is looked at. */
+#define FIGH_DESIGN_MAX_COLS 96 /* the packed factor (37 KB at 96) and the exchange buffers share 64 KB of LDS */
+int figh_design_gram(const double *d_R, int64_t ldr, int64_t N, int c, int n, const double *d_w, double *h_M);
+int figh_design_scores(const double *d_R, int64_t ldr, int64_t N, int c, int n, const double *h_L, double *d_trace,
+                       double *d_det_add, double *d_det_rm);
 
 /* ------------------------------------------------------------------ multi-GPU (RCCL over xGMI), SURVEY.md section 8e
  * One process per GPU.  Rank 0 calls figh_comm_unique_id and ships the 128 bytes to the other ranks by any
