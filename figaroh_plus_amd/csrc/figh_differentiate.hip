@@ -10,6 +10,7 @@
 // correctly rounded operations: this translation unit is compiled without FMA contraction, so those results are bit-equal to
 // SciPy's / NumPy's.  Only the SO(2) / SE(3) logarithms go through the device math library (acos, atan2, sin, cos, sqrt).
 #include "figh_internal.h"
+#include "figh_spatial.h"
 
 using namespace figh;
 
@@ -103,21 +104,6 @@ struct M3 {
     double m[3][3];
 };
 
-// identification_tools._quat_to_rot
-__device__ __forceinline__ M3 quat_to_rot(const double x, const double y, const double z, const double w) {
-    M3 R;
-    R.m[0][0] = 1 - 2 * (y * y + z * z);
-    R.m[0][1] = 2 * (x * y - z * w);
-    R.m[0][2] = 2 * (x * z + y * w);
-    R.m[1][0] = 2 * (x * y + z * w);
-    R.m[1][1] = 1 - 2 * (x * x + z * z);
-    R.m[1][2] = 2 * (y * z - x * w);
-    R.m[2][0] = 2 * (x * z - y * w);
-    R.m[2][1] = 2 * (y * z + x * w);
-    R.m[2][2] = 1 - 2 * (x * x + y * y);
-    return R;
-}
-
 // identification_tools._log3, branch for branch
 __device__ __forceinline__ void log3(const M3 &R, double (&out)[3]) {
     double tr = ((R.m[0][0] + R.m[1][1] + R.m[2][2]) - 1.0) / 2.0;
@@ -148,7 +134,9 @@ __device__ __forceinline__ void log3(const M3 &R, double (&out)[3]) {
 
 // free-flyer: log6(R0^T R1, R0^T (p1 - p0)), (linear, angular) -- identification_tools.joint_difference / _log6
 __device__ __forceinline__ void freeflyer_difference(const double *q0, const double *q1, double (&v)[3], double (&w)[3]) {
-    const M3 R0 = quat_to_rot(q0[3], q0[4], q0[5], q0[6]), R1 = quat_to_rot(q1[3], q1[4], q1[5], q1[6]);
+    M3 R0, R1;  // identification_tools._quat_to_rot
+    quat_to_rotation(q0[3], q0[4], q0[5], q0[6], &R0.m[0][0]);
+    quat_to_rotation(q1[3], q1[4], q1[5], q1[6], &R1.m[0][0]);
     const double dp[3] = {q1[0] - q0[0], q1[1] - q0[1], q1[2] - q0[2]};
     M3 R;
     double p[3];
@@ -227,11 +215,6 @@ __global__ __launch_bounds__(256) void joint_difference_kernel(const DiffPlan P,
     }
 }
 
-unsigned capped_grid(const long items, const long per_group) {
-    const long g = (items + per_group - 1) / per_group;
-    return (unsigned)(g < 1 ? 1 : g > kMaxGrid ? kMaxGrid : g);
-}
-
 // pairs per tile: both stages of a tile of 64 k pairs fit 64 KB of LDS, k <= 4 (one lane per pair of a 256-thread workgroup);
 // 0: the model is too wide.  (_lib.joint_difference_tile states the same rule for the tests and the bench tool.)
 int difference_tile(const DevModel &m) {
@@ -251,7 +234,7 @@ extern "C" int figh_medfilt_cols(const double *d_X, int64_t rows, int cols, int6
     if (int rc = ensure_device()) return rc;
     ProfileScope scope("medfilt_cols");
     const long L = rows / nblocks, total = (long)rows * cols;
-    const dim3 grid(capped_grid(total, 256)), block(256);
+    const dim3 grid(capped_grid(total, 256, kMaxGrid)), block(256);
 #define FIGH_MF_LAUNCH(K)                                                                                              \
     hipLaunchKernelGGL((medfilt_cols_kernel<K>), grid, block, 0, stream(), d_X, L, cols, (long)ldx, total, kernel_size, \
                        d_Y, (long)ldy)
@@ -276,8 +259,8 @@ extern "C" int figh_gradient_cols(const double *d_F, int64_t rows, int cols, int
     FIGH_REQUIRE(cols > 0 && ld >= cols && ldg >= cols && ncols_active >= 0 && ncols_active <= cols, "bad shape");
     if (int rc = ensure_device()) return rc;
     ProfileScope scope("gradient_cols");
-    hipLaunchKernelGGL(gradient_cols_kernel, dim3(capped_grid((long)rows * cols, 256)), dim3(256), 0, stream(), d_F,
-                       (long)rows, cols, (long)ld, ncols_active, h, d_h, d_G, (long)ldg);
+    hipLaunchKernelGGL(gradient_cols_kernel, dim3(capped_grid((long)rows * cols, 256, kMaxGrid)), dim3(256), 0, stream(),
+                       d_F, (long)rows, cols, (long)ld, ncols_active, h, d_h, d_G, (long)ldg);
     FIGH_HIP(hipGetLastError());
     return FIGH_OK;
 }

@@ -83,17 +83,6 @@ __device__ __forceinline__ void link_wrench(const double *vl, const double *w, c
     }
 }
 
-// motion of the parent seen from the child: (R, p) = child -> parent
-__device__ __forceinline__ void motion_to_child(const double *R, const double *p, const double *lin, const double *ang,
-                                                double *olin, double *oang) {
-    double t1[3], t2[3];
-    cross3(p, ang, t1);
-#pragma unroll
-    for (int d = 0; d < 3; ++d) t2[d] = lin[d] - t1[d];
-    rotT(R, t2, olin);
-    rotT(R, ang, oang);
-}
-
 // wrench of the child seen from the parent: lin = R f_lin, ang = R f_ang + p x lin
 __device__ __forceinline__ void wrench_to_parent(const double *R, const double *p, const double *f, double *o) {
     double t[3];
@@ -244,67 +233,11 @@ __global__ __launch_bounds__(64) void inverse_dynamics_tree_kernel(const DevMode
                 }
             }
             const double ax[3] = {M->axis[k][0], M->axis[k][1], M->axis[k][2]};
-            double Rj[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, pj[3] = {0, 0, 0}, vj[6] = {0, 0, 0, 0, 0, 0},
-                   aj[6] = {0, 0, 0, 0, 0, 0};
-            if (jt == FIGH_JT_REVOLUTE || jt == FIGH_JT_CONTINUOUS) {
-                double s, c;
-                if (jt == FIGH_JT_REVOLUTE) {
-                    sincos_angle(jq0, &s, &c);
-                } else {
-                    c = jq0;
-                    s = jq1;
-                }
-                rodrigues(ax, c, s, Rj);
-#pragma unroll
-                for (int d = 0; d < 3; ++d) {
-                    vj[3 + d] = ax[d] * jqd;
-                    aj[3 + d] = ax[d] * jqdd;
-                }
-            } else if (jt == FIGH_JT_PRISMATIC) {
-#pragma unroll
-                for (int d = 0; d < 3; ++d) {
-                    pj[d] = ax[d] * jq0;
-                    vj[d] = ax[d] * jqd;
-                    aj[d] = ax[d] * jqdd;
-                }
-            } else {  // free-flyer: q = [p, qx qy qz qw], v in the joint's local frame
-                const int iq = M->idx_q[k], iv = M->idx_v[k];
-                const double x = qi[iq + 3], y = qi[iq + 4], z = qi[iq + 5], ww = qi[iq + 6];
-                Rj[0] = 1 - 2 * (y * y + z * z); Rj[1] = 2 * (x * y - z * ww); Rj[2] = 2 * (x * z + y * ww);
-                Rj[3] = 2 * (x * y + z * ww); Rj[4] = 1 - 2 * (x * x + z * z); Rj[5] = 2 * (y * z - x * ww);
-                Rj[6] = 2 * (x * z - y * ww); Rj[7] = 2 * (y * z + x * ww); Rj[8] = 1 - 2 * (x * x + y * y);
-#pragma unroll
-                for (int d = 0; d < 3; ++d) pj[d] = qi[iq + d];
-#pragma unroll
-                for (int d = 0; d < 6; ++d) {
-                    vj[d] = vi[iv + d];
-                    aj[d] = ai[iv + d];
-                }
-            }
+            double Rj[9], pj[3], vj[6], aj[6];
+            const int iq = M->idx_q[k], iv = M->idx_v[k];
+            joint_transform<true>(jt, ax, jq0, jq1, jqd, jqdd, qi + iq, vi + iv, ai + iv, 1, Rj, pj, vj, aj);
             double Rk[9], pk[3];  // liMi = placement * M_joint(q)
-            matmul3(M->placement[k], Rj, Rk);
-            rot(M->placement[k], pj, pk);
-#pragma unroll
-            for (int d = 0; d < 3; ++d) pk[d] += M->placement[k][9 + d];
-            double Vk[6], Ak[6];
-            motion_to_child(Rk, pk, V, V + 3, Vk, Vk + 3);
-            motion_to_child(Rk, pk, A, A + 3, Ak, Ak + 3);
-#pragma unroll
-            for (int d = 0; d < 6; ++d) Vk[d] += vj[d];
-            double c1[3], c2[3], c3[3];  // Vk x vj
-            cross3(Vk + 3, vj, c1);
-            cross3(Vk, vj + 3, c2);
-            cross3(Vk + 3, vj + 3, c3);
-#pragma unroll
-            for (int d = 0; d < 3; ++d) {
-                Ak[d] += aj[d] + c1[d] + c2[d];
-                Ak[3 + d] += aj[3 + d] + c3[d];
-            }
-#pragma unroll
-            for (int d = 0; d < 6; ++d) {
-                V[d] = Vk[d];
-                A[d] = Ak[d];
-            }
+            tree_forward_step(M->placement[k], Rj, pj, vj, aj, V, A, Rk, pk);
             if (plan.bslot[k] >= 0) {
                 double *b = br + (long)plan.bslot[k] * kDynBranchState * 64;
 #pragma unroll

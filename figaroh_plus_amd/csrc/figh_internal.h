@@ -127,6 +127,14 @@ enum WorkspaceSlot {
     kWorkspaceSlots
 };
 
+// Launch geometry of the kernels that loop over what a capped grid leaves: ceil(items / per_group) workgroups, at least one,
+// at most `cap` (each unit keeps its own), and the cap on grid rows (y: the batch index of a launch)
+inline unsigned capped_grid(const long items, const long per_group, const long cap) {
+    const long g = (items + per_group - 1) / per_group;
+    return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
+}
+inline unsigned capped_grid_rows(const long batch) { return (unsigned)(batch < 65535 ? batch : 65535); }
+
 // scratch buffer owned by the library, grown on demand (device)
 void *workspace(size_t bytes, WorkspaceSlot slot);
 

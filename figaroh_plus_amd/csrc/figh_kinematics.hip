@@ -29,7 +29,6 @@ namespace {
 constexpr int kStageCols = 12;              // columns staged per run: two joint blocks, or twelve Jacobian columns
 constexpr int kStageLd = kStageCols + 1;    // odd leading dimension of a staged row: lanes 26 dwords apart
 constexpr long kMaxGrid = 1 << 20;          // workgroups per launch; the kernels loop over the rest
-constexpr long kMaxGridY = 65535;           // parameter vectors per launch; the kernel loops over the rest
 
 enum { kModeR = 0, kModeJ = 1, kModeJSub = 2 };
 
@@ -88,34 +87,18 @@ __device__ __forceinline__ void mul_right(double *R, double *p, const double *Rb
     for (int d = 0; d < 3; ++d) p[d] += t[d];
 }
 
-// M_j(q_j): rotation about / translation along the axis, or the free-flyer's (p, quaternion x y z w)
+// M_j(q_j) of joint j of the model for the sample at qi.  (The outputs are preset although joint_transform writes all of
+// them: without these stores the walk kernels and calib_fkm_kernel are allocated 1 .. 6 other VGPRs than before,
+// profiles/rigid_body_ab.txt.)
 __device__ __forceinline__ void joint_motion(const DevModel *M, const int j, const double *qi, double *Rj, double *pj) {
     const int jt = M->jtype[j], iq = M->idx_q[j];
     const double ax[3] = {M->axis[j][0], M->axis[j][1], M->axis[j][2]};
 #pragma unroll
     for (int d = 0; d < 9; ++d) Rj[d] = (d % 4 == 0) ? 1.0 : 0.0;
     pj[0] = pj[1] = pj[2] = 0.0;
-    if (jt == FIGH_JT_REVOLUTE || jt == FIGH_JT_CONTINUOUS) {
-        double s, c;
-        if (jt == FIGH_JT_REVOLUTE) {
-            sincos_angle(qi[iq], &s, &c);
-        } else {
-            c = qi[iq];
-            s = qi[iq + 1];
-        }
-        rodrigues(ax, c, s, Rj);
-    } else if (jt == FIGH_JT_PRISMATIC) {
-        const double x = qi[iq];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) pj[d] = ax[d] * x;
-    } else {
-        const double x = qi[iq + 3], y = qi[iq + 4], z = qi[iq + 5], w = qi[iq + 6];
-        Rj[0] = 1 - 2 * (y * y + z * z); Rj[1] = 2 * (x * y - z * w); Rj[2] = 2 * (x * z + y * w);
-        Rj[3] = 2 * (x * y + z * w); Rj[4] = 1 - 2 * (x * x + z * z); Rj[5] = 2 * (y * z - x * w);
-        Rj[6] = 2 * (x * z - y * w); Rj[7] = 2 * (y * z + x * w); Rj[8] = 1 - 2 * (x * x + y * y);
-#pragma unroll
-        for (int d = 0; d < 3; ++d) pj[d] = qi[iq + d];
-    }
+    // (sin q is read only where there is one: behind the q of the last joint the row ends)
+    const double sin_q = jt == FIGH_JT_CONTINUOUS ? qi[iq + 1] : 0.0;
+    joint_transform<false>(jt, ax, qi[iq], sin_q, 0.0, 0.0, qi + iq, nullptr, nullptr, 1, Rj, pj, nullptr, nullptr);
 }
 
 // Column c of Ad(X) for X = (R, p): c < 3: (R[:, c], 0); c >= 3: (p x R[:, c - 3], R[:, c - 3])
@@ -339,11 +322,6 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const double *__restri
     }
 }
 
-unsigned capped(const long items, const long per) {
-    const long g = (items + per - 1) / per;
-    return (unsigned)(g < 1 ? 1 : g > kMaxGrid ? kMaxGrid : g);
-}
-
 void invert12(const double *P, double *out) {  // (R, p)^-1 = (R^T, -R^T p)
     for (int r = 0; r < 3; ++r)
         for (int c = 0; c < 3; ++c) out[3 * r + c] = P[3 * c + r];
@@ -446,7 +424,7 @@ extern "C" int figh_kinematic_regressor(figh_model_t model, int64_t N, const dou
     const long rows = (long)nmeas * N;
     int first[kMaxJoints], width[kMaxJoints];
     const long ntiles = (N + 63) / 64;
-    const unsigned grid = capped(ntiles, 1);
+    const unsigned grid = capped_grid(ntiles, 1, kMaxGrid);
     ProfileScope scope("kinematic_regressor");
     if (want_R) {
         KinPlan P = {};
@@ -519,8 +497,8 @@ extern "C" int figh_kinematic_regressor(figh_model_t model, int64_t N, const dou
                                    d_q, (long)ldq, meas_mask, d_J, (long)ldj, (double *)nullptr);
         }
         if (relative && d_rowsq_J)
-            hipLaunchKernelGGL(row_sumsq_kernel, dim3(capped(rows, 256)), dim3(256), 0, stream(), d_J, rows, m.nv, (long)ldj,
-                               d_rowsq_J);
+            hipLaunchKernelGGL(row_sumsq_kernel, dim3(capped_grid(rows, 256, kMaxGrid)), dim3(256), 0, stream(), d_J, rows,
+                               m.nv, (long)ldj, d_rowsq_J);
     }
     FIGH_HIP(hipGetLastError());
     return FIGH_OK;
@@ -564,7 +542,7 @@ extern "C" int figh_calib_fkm_batch(figh_model_t model, int64_t B, int64_t N, co
         P.Ps[d] = start_joint >= 0 ? h_start_placement[d] : (d < 9 && d % 4 == 0 ? 1.0 : 0.0);
     }
     ProfileScope scope("calib_fkm_batch");
-    hipLaunchKernelGGL(calib_fkm_kernel, dim3(capped(N, 256), (unsigned)(B < kMaxGridY ? B : kMaxGridY)), dim3(256), 0, stream(),
+    hipLaunchKernelGGL(calib_fkm_kernel, dim3(capped_grid(N, 256, kMaxGrid), capped_grid_rows(B)), dim3(256), 0, stream(),
                        model->dev, P, (long)B, (long)N, d_q, (long)ldq, n_chain, d_placements, d_wMo, d_eeMf, meas_mask, d_out,
                        (long)ld_out);
     FIGH_HIP(hipGetLastError());
@@ -578,8 +556,8 @@ extern "C" int figh_gather_rows(const double *d_W, int64_t ldw, int cols, const 
     if (n == 0) return FIGH_OK;
     FIGH_REQUIRE(d_W && d_row_idx && d_out, "NULL pointer");
     ProfileScope scope("gather_rows");
-    hipLaunchKernelGGL(gather_rows_kernel, dim3(capped((long)n * cols, 256)), dim3(256), 0, stream(), d_W, (long)ldw, cols,
-                       d_row_idx, (long)n, d_out, (long)ld_out);
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(capped_grid((long)n * cols, 256, kMaxGrid)), dim3(256), 0, stream(), d_W,
+                       (long)ldw, cols, d_row_idx, (long)n, d_out, (long)ld_out);
     FIGH_HIP(hipGetLastError());
     return FIGH_OK;
 }

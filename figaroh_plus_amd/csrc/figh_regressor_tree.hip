@@ -272,7 +272,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FC ? 1 : 2))
             int op = tape[pcnt].op, oa = tape[pcnt].a, ob = tape[pcnt].b, oc = tape[pcnt].c, od = tape[pcnt].d,
                 oe = tape[pcnt].e;
             if (op == OP_STEP) {
-                // ---- forward step onto joint k (restates the first loop of pinocchio::computeJointTorqueRegressor)
+                // ---- forward step onto joint k (restates the first loop of pinocchio::computeJointTorqueRegressor).
+                // A hand copy of joint_transform / tree_forward_step (figh_spatial.h: a fix there belongs here too); the Rc, pc
+                // update below is one of figh_kinematics.hip's mul_right.  Through the helpers registers and f64 instructions
+                // stayed equal, but W of the free-flyer walks differed by one rounding in 0.06 .. 1.8 % of its entries (the
+                // products are contracted into other FMAs), through mul_right alone as well (profiles/rigid_body_ab.txt).
                 const int k = oa;
                 const int jt = M->jtype[k], iq = M->idx_q[k], iv = M->idx_v[k];
                 const double ax[3] = {M->axis[k][0], M->axis[k][1], M->axis[k][2]};
@@ -378,11 +382,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FC ? 1 : 2))
                     for (int s = 0; s < NS; ++s)
                         if ((jmask >> s) & 1) {
                             double nJl[3], nJa[3];
-                            cross3(pk, Ja[s], t1);
-#pragma unroll
-                            for (int d = 0; d < 3; ++d) t2[d] = Jl[s][d] - t1[d];
-                            rotT(Rk, t2, nJl);
-                            rotT(Rk, Ja[s], nJa);
+                            motion_to_child(Rk, pk, Jl[s], Ja[s], nJl, nJa);
 #pragma unroll
                             for (int d = 0; d < 3; ++d) {
                                 Jl[s][d] = nJl[d];

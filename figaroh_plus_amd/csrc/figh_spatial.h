@@ -1,7 +1,9 @@
-// 3-vector / rotation helpers of the regressor kernels (fp64, 6-vectors are (linear, angular)).
+// 3-vector / rotation helpers and the rigid-body step of the device kernels (fp64, 6-vectors are (linear, angular)).
 #pragma once
 
 #include <hip/hip_runtime.h>
+
+#include "figh.h"
 
 namespace figh {
 
@@ -53,6 +55,110 @@ __device__ __forceinline__ void sincos_angle(double x, double *s, double *c) {
     const double n = (ax >= 0x1p30 && ax < 0x1p45) ? rint(x * 0x1.45f306dc9c883p-3) : 0.0;
     const double r = fma(-n, 0x1.1a62633145c07p-52, fma(-n, 0x1.921fb54442d18p+2, x));
     sincos(r, s, c);
+}
+
+// ---- the rigid-body step of a tree walk, written once (plain pointers, no DevModel).  regressor_tape_kernel keeps hand
+// copies of the joint model and the forward step: see the comment there.
+
+// rotation of the unit quaternion (x y z w), row-major
+__device__ __forceinline__ void quat_to_rotation(const double x, const double y, const double z, const double w, double *R) {
+    R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - z * w); R[2] = 2 * (x * z + y * w);
+    R[3] = 2 * (x * y + z * w); R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - x * w);
+    R[6] = 2 * (x * z - y * w); R[7] = 2 * (y * z + x * w); R[8] = 1 - 2 * (x * x + y * y);
+}
+
+// The joint model M_j(q_j) = (Rj, pj) and, with RATES, the joint's own velocity and acceleration (vj, aj; unused otherwise).
+// A single-dof joint takes x0 = q (cos q for a continuous joint), x1 = sin q (continuous only), xd, xdd; a free-flyer reads
+// its q = [p, qx qy qz qw] and its v, a (joint frame) from qf, vf, af, `stride` doubles apart (1: sample-major inputs).
+// Every branch writes every output and ends on the same element: with outputs preset by the caller the branches' last
+// stores went to different elements, the compiler merged them into one store through a selected address, and the arrays
+// behind it stayed in scratch (32 bytes per lane in inverse_dynamics_tree_kernel).
+template <bool RATES>
+__device__ __forceinline__ void joint_transform(const int jtype, const double *ax, const double x0, const double x1,
+                                                const double xd, const double xdd, const double *qf, const double *vf,
+                                                const double *af, const int stride, double *Rj, double *pj, double *vj,
+                                                double *aj) {
+    if (jtype == FIGH_JT_REVOLUTE || jtype == FIGH_JT_CONTINUOUS) {
+        double s = x1, c = x0;
+        if (jtype == FIGH_JT_REVOLUTE) sincos_angle(x0, &s, &c);
+        rodrigues(ax, c, s, Rj);
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            pj[d] = 0.0;
+            if constexpr (RATES) {
+                vj[d] = 0.0;
+                aj[d] = 0.0;
+                vj[3 + d] = ax[d] * xd;
+                aj[3 + d] = ax[d] * xdd;
+            }
+        }
+    } else if (jtype == FIGH_JT_PRISMATIC) {
+#pragma unroll
+        for (int d = 0; d < 9; ++d) Rj[d] = (d % 4 == 0) ? 1.0 : 0.0;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            pj[d] = ax[d] * x0;
+            if constexpr (RATES) {
+                vj[d] = ax[d] * xd;
+                aj[d] = ax[d] * xdd;
+                vj[3 + d] = 0.0;
+                aj[3 + d] = 0.0;
+            }
+        }
+    } else {
+        quat_to_rotation(qf[3 * stride], qf[4 * stride], qf[5 * stride], qf[6 * stride], Rj);
+#pragma unroll
+        for (int d = 0; d < 3; ++d) pj[d] = qf[d * stride];
+        if constexpr (RATES) {
+#pragma unroll
+            for (int d = 0; d < 6; ++d) {
+                vj[d] = vf[d * stride];
+                aj[d] = af[d * stride];
+            }
+        }
+    }
+}
+
+// motion of the parent seen from the child: (R, p) = child -> parent
+__device__ __forceinline__ void motion_to_child(const double *R, const double *p, const double *lin, const double *ang,
+                                                double *olin, double *oang) {
+    double t1[3], t2[3];
+    cross3(p, ang, t1);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) t2[d] = lin[d] - t1[d];
+    rotT(R, t2, olin);
+    rotT(R, ang, oang);
+}
+
+// Forward step of a tree walk onto a joint (the first loop of pinocchio::computeJointTorqueRegressor / rnea): with
+// liMi = (Rk, pk) = placement . M_j(q), (V, A) of the parent become (V, A) of the link, V = liMi^-1 V + vj,
+// A = liMi^-1 A + aj + V x vj.  placement: 9 rotation entries, then the translation.
+__device__ __forceinline__ void tree_forward_step(const double *placement, const double *Rj, const double *pj,
+                                                  const double *vj, const double *aj, double *V, double *A, double *Rk,
+                                                  double *pk) {
+    matmul3(placement, Rj, Rk);
+    rot(placement, pj, pk);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) pk[d] += placement[9 + d];
+    double Vk[6], Ak[6];
+    motion_to_child(Rk, pk, V, V + 3, Vk, Vk + 3);
+    motion_to_child(Rk, pk, A, A + 3, Ak, Ak + 3);
+#pragma unroll
+    for (int d = 0; d < 6; ++d) Vk[d] += vj[d];
+    double c1[3], c2[3], c3[3];  // Vk x vj
+    cross3(Vk + 3, vj, c1);
+    cross3(Vk, vj + 3, c2);
+    cross3(Vk + 3, vj + 3, c3);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        Ak[d] += aj[d] + c1[d] + c2[d];
+        Ak[3 + d] += aj[3 + d] + c3[d];
+    }
+#pragma unroll
+    for (int d = 0; d < 6; ++d) {
+        V[d] = Vk[d];
+        A[d] = Ak[d];
+    }
 }
 
 // J^T B for the body regressor B = bodyRegressor(v, a) of one link and a motion axis J = (Jl, Ja) expressed in the

@@ -31,7 +31,6 @@ using namespace figh;
 namespace {
 
 constexpr long kMaxGrid = 1 << 16;               // workgroups per launch; every kernel loops over what is left
-constexpr long kMaxGridY = 65535;                // trajectories per launch; the kernels loop over the rest
 constexpr int kMaxQ = 7 * (kMaxJoints - 1);      // position columns of the widest model
 constexpr int kMaxV = 6 * (kMaxJoints - 1);      // velocity columns
 
@@ -155,11 +154,6 @@ __global__ __launch_bounds__(256) void excitation_constraints_kernel(const Const
     }
 }
 
-unsigned capped_grid(const long items) {
-    const long g = (items + 255) / 256;
-    return (unsigned)(g < 1 ? 1 : g > kMaxGrid ? kMaxGrid : g);
-}
-
 // The active joints as columns.  FIGH_ERR_UNSUPPORTED for a joint that is not one revolute or prismatic degree of freedom,
 // FIGH_ERR_INVALID for an index pair that is no joint of the model or is listed twice.
 int check_active_joints(const DevModel &m, const int n_act, const int32_t *idxq, const int32_t *idxv) {
@@ -221,10 +215,10 @@ extern "C" int figh_spline_sample(figh_model_t model, int64_t B, int n_wps, int 
     int *seg = (int *)(tps + n_wps);
     ProfileScope scope("spline_sample");
     FIGH_HIP(hipMemcpyAsync(tps, h_tps, sizeof(double) * n_wps, hipMemcpyHostToDevice, stream()));
-    hipLaunchKernelGGL(spline_prologue_kernel, dim3(capped_grid(ncoef + n_per)), dim3(256), 0, stream(), (long)B, n_wps, n_act,
-                       (long)n_per, 1.0 / freq, tps, d_wps, d_vel_wps, (long)vel_stride, d_acc_wps, (long)acc_stride, coef, seg,
-                       local);
-    hipLaunchKernelGGL(spline_sample_kernel, dim3(capped_grid(per_traj), (unsigned)(B < kMaxGridY ? B : kMaxGridY), 3), dim3(256), 0,
+    hipLaunchKernelGGL(spline_prologue_kernel, dim3(capped_grid(ncoef + n_per, 256, kMaxGrid)), dim3(256), 0, stream(),
+                       (long)B, n_wps, n_act, (long)n_per, 1.0 / freq, tps, d_wps, d_vel_wps, (long)vel_stride, d_acc_wps,
+                       (long)acc_stride, coef, seg, local);
+    hipLaunchKernelGGL(spline_sample_kernel, dim3(capped_grid(per_traj, 256, kMaxGrid), capped_grid_rows(B), 3), dim3(256), 0,
                        stream(), P, (long)B, (long)n_per, nseg, coef, seg, local, d_q0, d_q, (long)ldq, d_v, d_a, (long)ldv);
     FIGH_HIP(hipGetLastError());
     return FIGH_OK;
@@ -257,7 +251,7 @@ extern "C" int figh_excitation_constraints(figh_model_t model, int64_t B, int64_
     if (!d_idx) return FIGH_ERR_ALLOC;
     ProfileScope scope("excitation_constraints");
     if (n_idx > 0) FIGH_HIP(hipMemcpyAsync(d_idx, h_idx_waypoints, sizeof(int) * n_idx, hipMemcpyHostToDevice, stream()));
-    hipLaunchKernelGGL(excitation_constraints_kernel, dim3(capped_grid(n_con), (unsigned)(B < kMaxGridY ? B : kMaxGridY)), dim3(256),
+    hipLaunchKernelGGL(excitation_constraints_kernel, dim3(capped_grid(n_con, 256, kMaxGrid), capped_grid_rows(B)), dim3(256),
                        0, stream(), P, (long)B, (long)n_per, n_idx, d_idx, d_q, (long)ldq, d_v, (long)ldv, d_tau, d_out,
                        (long)ld_out);
     FIGH_HIP(hipGetLastError());
