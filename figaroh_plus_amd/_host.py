@@ -133,7 +133,8 @@ def null_rule_triangles(rows, pieces=1):
     return max(1, -(-int(rows) // 32) + max(1, int(pieces)))
 
 
-def null_rule_certified(absdiag, idx_base, idx_regroup, bounds, tol_qr, safety=2.0, phi=None, rows=None, pieces=1):
+def null_rule_certified(absdiag, idx_base, idx_regroup, bounds, tol_qr, safety=2.0, phi=None, rows=None, pieces=1,
+                        native_verdict=None):
     """A-posteriori GUARD for a factorisation that ran WITH the null-pivot rule (``figh_tsqr_null_pivot_tol``): True when the
     classification ``|R_kk| > tol_qr`` can be trusted to be the one plain Householder -- the reference's ``np.linalg.qr``,
     qrdecomposition.py:205-221 -- gives on the same matrix; not certified = the caller repeats the factorisation WITHOUT the
@@ -173,6 +174,10 @@ def null_rule_certified(absdiag, idx_base, idx_regroup, bounds, tol_qr, safety=2
     proof: the bound uses the per-triangle folding limit for |E| (a column that folds its maximum in EVERY triangle has a
     residual of its own near the tolerance scale and trips the second condition)."""
     import numpy as np
+    if native_verdict is not None:
+        # figh_chain_host_tail took the decision on the same numbers (the conditions below, one for one, safety = 2): this
+        # function stays the one place through which a pass is certified
+        return bool(native_verdict)
     if bounds is None:
         return False
     A_base, A_dep, xnorm = bounds

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # FIGH_LIB_PATH: another build of the same ABI (same-box A/B of kernel variants); default is the in-tree library
 LIB_PATH = os.environ.get("FIGH_LIB_PATH") or os.path.join(_HERE, "libfigh.so")
 
-ABI_VERSION = 112  # include/figh.h FIGH_ABI_VERSION: load() refuses a library of another ABI
+ABI_VERSION = 113  # include/figh.h FIGH_ABI_VERSION: load() refuses a library of another ABI
 
 FIGH_OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_ALLOC, ERR_UNSUPPORTED, ERR_COMM = -1, -2, -3, -4, -5
@@ -90,6 +90,10 @@ SIGNATURES = {
     "figh_regressor_tsqr_fused": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double,
                                             C.c_void_p]),
+    "figh_chain_host_tail": (C.c_int, [C.c_void_p]),
+    "figh_chain_pass_fused": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_void_p,
+                                        C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     "figh_tsqr_merge_base": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p]),
     "figh_compact_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_double, C.c_void_p,
                                     C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]),
@@ -712,6 +716,74 @@ def regressor_tsqr_fused(model, flags, N, d_q, d_v, d_a, d_W, ldw, d_colsq, d_ke
         return False
     check(rc)
     return True
+
+
+TAIL_OK, TAIL_SINGULAR = 0, 1
+
+
+class _HostTailStruct(C.Structure):
+    """figh_host_tail_t of include/figh.h"""
+    _fields_ = [("rows_k", C.c_void_p), ("n", C.c_int32), ("with_tau", C.c_int32), ("tol_qr", C.c_double),
+                ("total_rows", C.c_int64), ("pieces", C.c_int64), ("null_rule", C.c_int32), ("n_cached_base", C.c_int32),
+                ("cached_base", C.c_void_p), ("bounds", C.c_void_p), ("idx", C.c_void_p), ("absdiag", C.c_void_p),
+                ("beta", C.c_void_p), ("phi_ls", C.c_void_p), ("phi_b", C.c_void_p), ("residual_norm", C.c_double),
+                ("n_base", C.c_int32), ("status", C.c_int32), ("certified", C.c_int32), ("bounds_recomputed", C.c_int32)]
+
+
+class HostTail:
+    """The argument block of figh_chain_host_tail / figh_chain_pass_fused for problems of ``n`` columns (+ tau) with the
+    output arrays it points to, allocated once and overwritten by every call: copy what is to outlive the next one.
+    ``cache_of`` is whatever object the caller ties the validity of ``bounds`` / ``cached_base`` to (the pipeline: its
+    ``_cert_cache`` tuple)."""
+
+    def __init__(self, n, with_tau):
+        self.n, self.with_tau = int(n), bool(with_tau)
+        self.idx = np.zeros(self.n, dtype=np.int32)
+        self.cached_base = np.zeros(self.n, dtype=np.int32)
+        self.absdiag, self.phi_ls, self.phi_b = np.zeros(self.n), np.zeros(self.n), np.zeros(self.n)
+        self.beta = np.zeros(self.n * self.n)
+        self.bounds = np.zeros(self.n + 2)
+        self.cache_of = None
+        s = self.s = _HostTailStruct()
+        s.n, s.with_tau, s.n_cached_base = self.n, int(self.with_tau), -1
+        for name in ("cached_base", "bounds", "idx", "absdiag", "beta", "phi_ls", "phi_b"):
+            setattr(s, name, getattr(self, name).ctypes.data)
+        self.ref = C.addressof(s)
+
+    def keep_bounds(self, owner):
+        """The bounds just computed belong to this call's base columns and stay valid while ``cache_of is owner``."""
+        r = self.s.n_base
+        self.cached_base[:r] = self.idx[:r]
+        self.s.n_cached_base = r
+        self.cache_of = owner
+
+    def bounds_tuple(self):
+        """(A_base, A_dep, |R1^-1|_inf) as _host.null_rule_bounds returns them, None when they are not valid."""
+        if self.bounds[self.n + 1] == 0.0:
+            return None
+        r = self.s.n_base
+        return self.bounds[:r].copy(), self.bounds[r:self.n].copy(), float(self.bounds[self.n])
+
+
+def chain_host_tail(tail, rows_k):
+    """figh_chain_host_tail on ``rows_k`` ((nc + 1) x nc, C-contiguous float64): results in ``tail``'s arrays and ``tail.s``."""
+    tail.s.rows_k = rows_k.ctypes.data
+    check(load().figh_chain_host_tail(tail.ref))
+
+
+def chain_pass_fused(model, flags, N, d_q, d_v, d_a, d_W, ldw, d_kept, n, d_tau, tol_qr, tol_e, d_pack, h_pack, pack_bytes,
+                     kept_mask_u8, tail):
+    """One fused pass in one call (figh.h): None when the shape does not fuse (nothing launched), False when the device
+    selected other columns than ``kept_mask_u8`` (the pack is on the host, the tail was not run), True with the results in
+    ``tail``."""
+    changed = C.c_int(0)
+    rc = load().figh_chain_pass_fused(model.handle, flags, N, d_q.ptr, d_v.ptr, d_a.ptr, d_W.ptr, ldw, d_kept.ptr, n,
+                                      d_tau.ptr if d_tau is not None else None, tol_qr, tol_e, d_pack.ptr, h_pack, pack_bytes,
+                                      kept_mask_u8.ctypes.data, C.byref(changed), tail.ref)
+    if rc == ERR_UNSUPPORTED:
+        return None
+    check(rc)
+    return not changed.value
 
 
 def tsqr_merge_base(d_Rs, count, nc, n_free, tol_qr, d_Rk):

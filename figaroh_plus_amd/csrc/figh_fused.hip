@@ -637,11 +637,10 @@ static int launch_fused_batch(const figh_model_s *m, int flags, long B, long n_p
 
 using namespace figh;
 
-extern "C" int figh_regressor_tsqr_fused(figh_model_t model, int flags, int64_t N, const double *d_q, const double *d_v,
-                                         const double *d_a, double *d_W, int64_t ldw, double *d_colsq,
-                                         const int32_t *d_kept, int n, const double *d_tau, double tol_qr,
-                                         double *d_R_out) {
-    FIGH_REQUIRE(model && d_q && d_v && d_a && d_W && d_colsq && d_kept && d_R_out, "NULL pointer");
+// the checks and the launch of figh_regressor_tsqr_fused / figh_chain_pass_fused
+static int fused_pass_launch(figh_model_t model, int flags, int64_t N, const double *d_q, const double *d_v, const double *d_a,
+                             double *d_W, int64_t ldw, double *d_colsq, const int32_t *d_kept, int n, const double *d_tau,
+                             double **Rws, long *count) {
     FIGH_REQUIRE(N >= 0 && n >= 1, "bad shape");
     const DevModel &h = model->host;
     const int nc = n + (d_tau ? 1 : 0);
@@ -653,27 +652,66 @@ extern "C" int figh_regressor_tsqr_fused(figh_model_t model, int flags, int64_t 
         return FIGH_ERR_UNSUPPORTED;
     }
     if (int rc = ensure_device()) return rc;
-    double *Rws = nullptr;
-    long count = 0;
-    int rc;
     const int f = flags & 7;
     switch (h.nlinks) {
         case 5:
-            rc = launch_fused<5>(model, f, (long)N, d_q, d_v, d_a, d_W, d_tau, d_kept, n, d_colsq, &Rws, &count);
-            break;
+            return launch_fused<5>(model, f, (long)N, d_q, d_v, d_a, d_W, d_tau, d_kept, n, d_colsq, Rws, count);
         case 6:
-            rc = launch_fused<6>(model, f, (long)N, d_q, d_v, d_a, d_W, d_tau, d_kept, n, d_colsq, &Rws, &count);
-            break;
+            return launch_fused<6>(model, f, (long)N, d_q, d_v, d_a, d_W, d_tau, d_kept, n, d_colsq, Rws, count);
         case 7:
-            rc = launch_fused<7>(model, f, (long)N, d_q, d_v, d_a, d_W, d_tau, d_kept, n, d_colsq, &Rws, &count);
-            break;
+            return launch_fused<7>(model, f, (long)N, d_q, d_v, d_a, d_W, d_tau, d_kept, n, d_colsq, Rws, count);
         default:
             // (eight links: two 58 KB tile buffers leave 17 KB of the 160 KB of LDS, less than three consumer triangles)
             set_error("fused regressor + TSQR: serial chains of 5 to 7 joints (LDS: two tile buffers + three consumer triangles)");
             return FIGH_ERR_UNSUPPORTED;
     }
-    if (rc) return rc;
-    return tsqr_reduce_stack(Rws, count, nc, n, tol_qr, d_R_out);
+}
+
+extern "C" int figh_regressor_tsqr_fused(figh_model_t model, int flags, int64_t N, const double *d_q, const double *d_v,
+                                         const double *d_a, double *d_W, int64_t ldw, double *d_colsq,
+                                         const int32_t *d_kept, int n, const double *d_tau, double tol_qr,
+                                         double *d_R_out) {
+    FIGH_REQUIRE(model && d_q && d_v && d_a && d_W && d_colsq && d_kept && d_R_out, "NULL pointer");
+    double *Rws = nullptr;
+    long count = 0;
+    if (int rc = fused_pass_launch(model, flags, N, d_q, d_v, d_a, d_W, ldw, d_colsq, d_kept, n, d_tau, &Rws, &count))
+        return rc;
+    return tsqr_reduce_stack(Rws, count, n + (d_tau ? 1 : 0), n, tol_qr, d_R_out);
+}
+
+extern "C" int figh_chain_pass_fused(figh_model_t model, int flags, int64_t N, const double *d_q, const double *d_v,
+                                     const double *d_a, double *d_W, int64_t ldw, const int32_t *d_kept, int n,
+                                     const double *d_tau, double tol_qr, double tol_e, double *d_pack, double *h_pack,
+                                     size_t pack_bytes, const uint8_t *h_kept_mask, int *changed, figh_host_tail_t *tail) {
+    FIGH_REQUIRE(model && d_q && d_v && d_a && d_W && d_kept && d_pack && h_pack && h_kept_mask && changed && tail,
+                 "NULL pointer");
+    FIGH_REQUIRE(tol_qr >= 0.0, "figh_chain_pass_fused: the rank decision needs tol_qr >= 0");
+    const int ncols = 14 * model->host.nlinks, nc = n + (d_tau ? 1 : 0);
+    const size_t sel_words = (size_t)(2 + 2 * ncols + 1) / 2;
+    const size_t words = (size_t)ncols + sel_words + (size_t)(nc > 0 ? (nc + 1) * nc : 0);
+    FIGH_REQUIRE(n >= 1 && pack_bytes >= sizeof(double) * words, "figh_chain_pass_fused: the pack is [colsq | sel | rows]");
+    FIGH_REQUIRE(tail->n == n && (tail->with_tau != 0) == (d_tau != nullptr), "figh_chain_pass_fused: tail of another shape");
+    double *d_colsq = d_pack, *d_rows = d_pack + ncols + sel_words;
+    int32_t *d_sel = reinterpret_cast<int32_t *>(d_pack + ncols);
+    double *Rws = nullptr;
+    long count = 0;
+    if (int rc = fused_pass_launch(model, flags, N, d_q, d_v, d_a, d_W, ldw, d_colsq, d_kept, n, d_tau, &Rws, &count)) return rc;
+    // One stream, the order of the separate entries: norms, merge tree, selection, one copy.  (Norms and selection on the
+    // side stream, beside the merge tree, were measured: 10 us less per warm step, but the host's wait then returned on a
+    // 150 us grid during the first forty passes of a process -- profiles/chain_pass_tail_ab.txt.)
+    if (int rc = tsqr_reduce_stack(Rws, count, nc, n, tol_qr, d_rows)) return rc;
+    if (int rc = figh_select_columns(d_colsq, ncols, tol_e, 14, d_sel)) return rc;
+    FIGH_HIP(hipMemcpyAsync(h_pack, d_pack, sizeof(double) * words, hipMemcpyDeviceToHost, stream()));
+    FIGH_HIP(hipStreamSynchronize(stream()));
+    const int32_t *mask_now = reinterpret_cast<const int32_t *>(h_pack + ncols) + 2 + ncols;
+    *changed = 0;
+    for (int c = 0; c < ncols; ++c)
+        if ((mask_now[c] != 0) != (h_kept_mask[c] != 0)) {
+            *changed = 1;
+            return FIGH_OK;
+        }
+    tail->rows_k = h_pack + ncols + sel_words;
+    return figh_chain_host_tail(tail);
 }
 
 // The smallest trajectory the batched launch takes: one full sample tile.  64 samples are at least 320 rows, more than the

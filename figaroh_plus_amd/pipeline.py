@@ -82,12 +82,19 @@ def _solve_upper(R1, B):
 class IdentificationPipeline:
     def __init__(self, robot, param, params_std=None, coupling=False, tol_e=1e-6, tol_qr=qrd.TOL_QR, exchange=None,
                  chunk_samples=None, placement_trials=1, structural_zeros="every-pass", w_layout="dense", fuse=True, null_pivots=True,
-                 row_blocks=None):
+                 row_blocks=None, native_tail=True):
         """``chunk_samples``: when the stacked regressor of all N samples does not fit HBM (human model at 1e7
         samples: 269 GB) the samples are processed in chunks of this size -- pass 1 accumulates diag(W^T W), pass 2
         rebuilds each chunk's W (recomputing is far cheaper than storing), factors it and stacks the triangles,
         which ``figh_tsqr_merge`` reduces.  Results are those of the one-shot pass (R is row-order independent)."""
         self.chunk_samples = chunk_samples
+        # native_tail: the host tail of problems with at most 80 kept columns runs in libfigh (figh_chain_host_tail), and a
+        # fused pass of a single rank is ONE call (figh_chain_pass_fused: launches, copy, wait, check of the selection, tail).
+        # False keeps the NumPy / LAPACK tail and one call per launch (tests, A/B runs).
+        self.native_tail = bool(native_tail)
+        self._host_tail = None
+        self._strings_memo = None
+        self.strings_memo_hits = 0
         # row_blocks (ACTIVE JOINTS, examples/tiago/identification.py:148-187, :406-424): the dof indices (``act_idxv``) whose
         # row blocks carry measurements.  As in the script, the columns are eliminated on the norms of the FULL regressor
         # (every row block is walked for diag(W^T W)), but only the listed blocks are stored, and only they -- with their tau
@@ -647,6 +654,8 @@ class IdentificationPipeline:
         ncols, with_tau = W.ref_cols, self.d_tau is not None
         nc = n + (1 if with_tau else 0)
         local = not getattr(ex, "collective", True)
+        if local and self.native_tail and nc <= 80:
+            return self._run_fused_native(handle, flags, strings, mask, d_kept, n, nc, with_tau)
         if not _lib.regressor_tsqr_fused(handle, flags, self.N, self.d_q, self.d_v, self.d_a, W.buf, W.ld, self._d_colsq,
                                          d_kept, n, self.d_tau, self.tol_qr if local else -1.0,
                                          self._d_rows if local else self._d_R):
@@ -679,6 +688,100 @@ class IdentificationPipeline:
             self._kept_cache = (mask.copy(), list(idx_e), list(params_r))
         rows_k = host[ncols + self._sel_words:].reshape(nc + 1, nc)
         return self._finish(rows_k, n, nc, params_r, idx_e, host[:ncols].copy(), with_tau, W.rows * ex.world_size, strings)
+
+    def _run_fused_native(self, handle, flags, strings, mask, d_kept, n, nc, with_tau):
+        """_run_fused for a single rank in one call (figh_chain_pass_fused): the launches, the copy of the pack, the wait, the
+        check of the selection and the host tail, without a return to Python in between."""
+        ex, W = self.exchange, self.W
+        ncols = W.ref_cols
+        pin = getattr(self, "_host_pack", None)
+        if pin is None or pin.size < self._d_pack.size:
+            pin = self._host_pack = _lib.PinnedArray(self._d_pack.size)
+        total_rows = W.rows * ex.world_size
+        tail = self._tail_args(n, with_tau, total_rows)
+        ok = _lib.chain_pass_fused(handle, flags, self.N, self.d_q, self.d_v, self.d_a, W.buf, W.ld, d_kept, n, self.d_tau,
+                                   self.tol_qr, self.tol_e, self._d_pack, pin.array.ctypes.data, 8 * pin.size,
+                                   mask.view(np.uint8), tail)
+        if ok is None:
+            self.fuse = False  # (this shape does not fuse: not asked again until the next set_samples)
+            return None
+        if not ok:
+            self._fused_kept = None  # the kept set changed: the two-launch path learns the new one
+            return None
+        self.fused_passes += 1
+        self._n_expected = n
+        cached = self._kept_cache
+        if cached is not None and np.array_equal(cached[0], mask):
+            idx_e, params_r = list(cached[1]), list(cached[2])
+        else:
+            idx_e = np.flatnonzero(~mask).tolist()
+            params_r = [self.names[i] for i in np.flatnonzero(mask).tolist()]
+            self._kept_cache = (mask.copy(), list(idx_e), list(params_r))
+        out = self._native_out(tail, n, params_r, idx_e, pin.array[:ncols].copy(), with_tau, total_rows, strings)
+        # EMPIRICAL, mechanism not understood (profiles/chain_pass_tail_ab.txt, section 5): during the first forty or so passes of
+        # a process, passes that follow each other without the NumPy / LAPACK tail start on a 149 us grid (steps of 1337 / 1487 /
+        # 1637 us whatever their kernels take).  Entering and leaving the single-thread BLAS context once per pass -- which that
+        # tail did, 8 us -- takes them off the grid; a busy wait of the same or a longer time does not.
+        with _single_threaded_blas(n):
+            pass
+        return out
+
+    def _tail_args(self, n, with_tau, total_rows):
+        """The argument block of the native host tail for this pass (allocated once per problem shape)."""
+        tail = self._host_tail
+        if tail is None or tail.n != n or tail.with_tau != bool(with_tau):
+            tail = self._host_tail = _lib.HostTail(n, with_tau)
+        s = tail.s
+        s.tol_qr, s.total_rows, s.pieces = self.tol_qr, int(total_rows), self._level0_pieces(total_rows)
+        s.null_rule = int(self.null_pivots)
+        # the certificate's coefficient sums are kept while the base set stays the same, as _finish keeps them
+        if self._cert_cache is None or tail.cache_of is not self._cert_cache:
+            s.n_cached_base = -1
+        return tail
+
+    def _native_out(self, tail, n, params_r, idx_e, col_norm, with_tau, total_rows, strings):
+        """What _finish returns, from the results of figh_chain_host_tail / figh_chain_pass_fused in ``tail``."""
+        s = tail.s
+        r = s.n_base
+        assert len(params_r) == n, "params_r does not have same length with R"
+        if self.null_pivots and s.bounds_recomputed:
+            self._cert_cache = ((n, tail.idx[:r].astype(np.int64).tobytes()), tail.bounds_tuple())
+            tail.keep_bounds(self._cert_cache)
+        if s.status == _lib.TAIL_SINGULAR:
+            raise np.linalg.LinAlgError("Singular matrix")
+        idx = tail.idx.tolist()
+        idx_base, idx_regroup = idx[:r], idx[r:]
+        beta = tail.beta[:r * (n - r)].reshape(r, n - r).copy()
+        absdiag = tail.absdiag.copy()
+        out = {
+            "idx_e": idx_e, "params_r": params_r, "idx_base": idx_base, "beta": beta,
+            "col_norm": col_norm, "absdiagR": absdiag, "rows": total_rows,
+        }
+        if self.null_pivots:
+            from . import _host
+            self._cert_args = (absdiag.copy(), idx_base, idx_regroup, self._cert_cache[1])
+            out["null_rule_certified"] = _host.null_rule_certified(*self._cert_args, self.tol_qr, rows=total_rows, pieces=s.pieces,
+                                                                   native_verdict=s.certified)
+        if strings:
+            out["params_base"] = self._expressions_memo(params_r, tail.idx.tobytes() + bytes((r,)), idx_base, idx_regroup, beta)
+        if with_tau:
+            out["phi_b"] = tail.phi_b[:r].copy()
+            out["phi_ls"] = tail.phi_ls[:r].copy()
+            out["residual_norm"] = float(s.residual_norm)
+        return out
+
+    def _expressions_memo(self, params_r, idx_key, idx_base, idx_regroup, beta):
+        """qrd._expressions, kept while its inputs are EXACTLY the same: the names of the kept columns (the kept mask), the
+        two index sets and the bytes of the rounded coefficients.  The rounded regrouping coefficients are geometric constants
+        of the robot, so the memo also hits with fresh samples; a miss costs what the call costs."""
+        memo = self._strings_memo
+        beta_key = (beta + 0.0).tobytes()  # (-0.0 -> 0.0: the sign of a coefficient that rounds to zero follows R's rounding)
+        if memo is not None and memo[1] == idx_key and memo[2] == beta_key and memo[0] == params_r:
+            self.strings_memo_hits += 1
+            return list(memo[3])
+        exprs = qrd._expressions([params_r[i] for i in idx_base], [params_r[i] for i in idx_regroup], beta)
+        self._strings_memo = (list(params_r), idx_key, beta_key, list(exprs))
+        return exprs
 
     def _block_tri(self, wls, nblocks, nc):
         """Device buffer for the per-row-block triangles of figh_tsqr_selected_blocks (kept for the weighted solve)."""
@@ -933,6 +1036,11 @@ class IdentificationPipeline:
         """Host tail on the n x n numbers the device returns (qrdecomposition.py:215-266): ``rows_k`` ((nc + 1) x nc) holds,
         in the original column order, the rows of the regrouped factorisation qr([W1 W2 tau]) at the base columns and, in
         its last row, the diagonal of the plain factorisation (include/figh.h, figh_tsqr_selected)."""
+        if self.native_tail and 1 <= n <= 80:
+            # (the same tail in libfigh, figh_chain_host_tail: this function's n <= 80 branch condition for condition)
+            tail = self._tail_args(n, with_tau, total_rows)
+            _lib.chain_host_tail(tail, np.ascontiguousarray(rows_k, dtype=np.float64))
+            return self._native_out(tail, n, params_r, idx_e, col_norm, with_tau, total_rows, strings)
         diag = np.abs(rows_k[nc])
         rows_k = rows_k[:nc]
         base_mask = diag[:n] > self.tol_qr  # the device took the same decision on the same numbers

@@ -91,7 +91,7 @@ typedef struct figh_model_s *figh_model_t;
  * (round 5 did so for figh_tsqr_selected_wrench / figh_regressor_build_padded without a bump: a library of the older ABI
  * accepts the longer argument list under cdecl and silently ignores the new arguments).  figaroh_plus_amd/_lib.py refuses a
  * library -- in-tree or FIGH_LIB_PATH -- whose figh_version() differs from the value it was written against. */
-#define FIGH_ABI_VERSION 112
+#define FIGH_ABI_VERSION 113
 int figh_version(void);
 const char *figh_last_error(void);
 int figh_device_count(int *count);
@@ -322,6 +322,56 @@ int figh_tsqr_selected(const double *d_W, int64_t rows, int64_t ldw, const doubl
 int figh_regressor_tsqr_fused(figh_model_t model, int flags, int64_t N, const double *d_q, const double *d_v,
                               const double *d_a, double *d_W, int64_t ldw, double *d_colsq, const int32_t *d_kept, int n,
                               const double *d_tau, double tol_qr, double *d_R_out);
+/* ---- the host tail of a pass on the numbers the device returns (get_baseParams, qrdecomposition.py:215-244, for at most
+ * 80 kept columns), HOST ONLY: no device is needed, opened or touched.
+ * In: rows_k = the (nc + 1) x nc output of figh_tsqr_selected / figh_regressor_tsqr_fused with tol_qr >= 0 (layout
+ * above; nc = n + with_tau), tol_qr, total_rows and pieces (the rows of the factored matrix and its separately launched
+ * parts: the certificate's margin grows with sqrt(T), T <= total_rows / 32 + pieces level-0 triangles), null_rule != 0:
+ * the pass ran under figh_tsqr_null_pivot_tol(tol_qr) and is to be certified.
+ * Out: idx = the base columns {k < n : |diag_k| > tol_qr} ascending (n_base of them; a NaN pivot is not base) followed
+ * by the others ascending; absdiag (n) = |diag|; beta (n_base x (n - n_base), packed) = R1^-1 R2 rounded to six
+ * decimals as np.around rounds (round-half-even of x 1e6, divided back); with_tau: phi_ls = R1^-1 Q1^T tau, phi_b = phi_ls
+ * rounded likewise, residual_norm = |rows_k[n][n]|.  R1^-1 comes from back substitution on the UPPER triangle of
+ * rows_k[base][:, base] (below it the device leaves rounding residues).  status = FIGH_TAIL_SINGULAR when R1 has an exactly
+ * zero pivot (beta, phi_* are then not written; np.linalg.inv of the reference raises LinAlgError).
+ * Certificate (null_rule): certified = 1 when the classification is provably plain Householder's -- every base pivot
+ * further above tol_qr than 2 (1 + A_base[k]) sqrt(T) tol_qr / 64, every other pivot finite, at most tol_qr / 8 and
+ * further below tol_qr than 2 (1 + A_dep[c]) tol_qr / 64, and (with_tau) |R1^-1|_inf (tol_qr / 64) |phi|_1 <=
+ * 1e-7 max(1, |phi|_inf).  bounds (n + 2 doubles, in / out) = [A_base (n_base) | A_dep (n - n_base) | |R1^-1|_inf | valid]:
+ * A_base[k] = |R1_kk| sum_{i<k} |(R1^-1)_ik|, A_dep[c] = sum_i |(R1^-1 R2)_ic|; valid = 0 when R1 is singular or its inverse
+ * not finite (never certified).  They are properties of the model far more than of the samples: when the caller hands
+ * back the base columns they were computed for (cached_base, n_cached_base; -1: none) and those are this pass's, bounds is
+ * used as it is; otherwise it is recomputed and bounds_recomputed = 1. */
+enum { FIGH_TAIL_OK = 0, FIGH_TAIL_SINGULAR = 1 };
+typedef struct figh_host_tail_s {
+    const double *rows_k;        /* in (figh_chain_pass_fused: set by the entry to the staged rows) */
+    int32_t n, with_tau;         /* in */
+    double tol_qr;               /* in */
+    int64_t total_rows, pieces;  /* in */
+    int32_t null_rule;           /* in */
+    int32_t n_cached_base;       /* in */
+    const int32_t *cached_base;  /* in */
+    double *bounds;              /* in / out: n + 2 */
+    int32_t *idx;                /* out: n */
+    double *absdiag;             /* out: n */
+    double *beta;                /* out: up to n * n / 4 */
+    double *phi_ls, *phi_b;      /* out: n_base each (with_tau) */
+    double residual_norm;        /* out */
+    int32_t n_base, status, certified, bounds_recomputed; /* out */
+} figh_host_tail_t;
+int figh_chain_host_tail(figh_host_tail_t *tail);
+/* One call for a whole fused pass of a single rank: figh_regressor_tsqr_fused (same arguments, same launches, tol_qr >= 0),
+ * figh_select_columns(d_colsq, 14 nlinks, tol_e, 14, d_sel) behind it on the library stream, one copy of the pack to the
+ * host, the wait, the check of the selection and figh_chain_host_tail on the staged rows.  d_pack = [colsq (ncols f64) | sel (2 + 2 ncols i32, padded to 8
+ * bytes) | rows ((nc + 1) nc f64)], ncols = 14 nlinks: d_colsq, d_sel and d_R_out of the separate entries are its three
+ * parts; h_pack (pack_bytes, page-locked: figh_host_alloc) receives it.  h_kept_mask (ncols bytes): the 0 / 1 mask of
+ * d_kept.  *changed = 1 when the device's selection is another one: the pass is to be discarded and repeated through
+ * figh_regressor_build + figh_tsqr_selected, tail is not touched.  col_norm and sel are bit for bit those of the separate
+ * entries (same kernels, same order of the sums).  FIGH_ERR_UNSUPPORTED as for figh_regressor_tsqr_fused. */
+int figh_chain_pass_fused(figh_model_t model, int flags, int64_t N, const double *d_q, const double *d_v, const double *d_a,
+                          double *d_W, int64_t ldw, const int32_t *d_kept, int n, const double *d_tau, double tol_qr,
+                          double tol_e, double *d_pack, double *h_pack, size_t pack_bytes, const uint8_t *h_kept_mask,
+                          int *changed, figh_host_tail_t *tail);
 /* figh_tsqr_selected for the external-wrench regressor of a model with a free-flyer root (regressor.py:89-192: six row
  * blocks of rows / 6 rows, force components first): in the force rows the six rotational-inertia columns of every link
  * are exact zeros, so those rows are factored over the nf_expected kept columns with slot >= 6 only (2 m nf^2 instead of
