@@ -59,6 +59,11 @@ from ._host import relative_percent as _relative_percent
 from ._host import single_threaded_blas as _single_threaded_blas
 
 
+def _grown(buf, size, alloc):
+    """``buf`` while it holds ``size`` elements, else ``alloc(size)``: grow-only buffers (an allocation synchronises the device)."""
+    return buf if buf is not None and buf.size >= size else alloc(size)
+
+
 def _dtrtri(R1):
     from scipy.linalg.lapack import dtrtri
     return dtrtri(R1, lower=0)  # reads the upper triangle only
@@ -80,6 +85,24 @@ def _solve_upper(R1, B):
 
 
 class IdentificationPipeline:
+    """State by lifetime.  Every attribute exists after ``__init__``; a group is initialised by the one method named with it,
+    which is also its only reset point.  (bench.py, tests and tools read these names: they are an interface.)
+
+    group [method] -- attributes -- reset by
+    configuration -- constructor arguments, names, params_std, _fuse_requested, _null_pivots_requested -- never
+    sample set [_init_samples] -- N, d_q, d_v, d_a, d_tau, _in_flags, repack_ms, fuse, null_pivots, _force_compact_ok -- set_samples
+    resident W and its layout [_init_layout; written by _allocate_resident alone] -- W, _padded, _compact, _link_pos, _d_link_pos,
+        _force_ld, _zeros_once, _sel_words, _d_pack and its views _d_colsq / _d_sel / _d_rows, _d_R, _hint_blocks, _wrench_split,
+        _tree_blocks, _padded_flags -- whatever drops W (set_samples, _drop_resident)
+    learnt from earlier passes [forget] -- _kept_cache None, _n_expected -1, _nf_expected -1, _mask_expected None, _block_cache None
+        (these five: _forget_columns, also when a W is allocated), _fused_kept None, _chunk_kept None (also when _dc_idx is
+        re-allocated), _cert_cache None (also by set_samples and the fallback of run()) -- forget()
+    buffers that outlive all of that -- _host_pack, _d_kept_buf, _scratch (the _sb pool), _d_block_tri, _dc_colsq, _dc_idx, _dc_R,
+        _d_tailpack, _host_tailpack, _host_tail, _strings_memo, _force_slot_mask, _own_handle, _ancestors -- never (grown on demand)
+    one pass only [_init_pass] -- _have_block_tri, _beta_later, _cert_args -- start of _run_once
+    counters and diagnostics -- fused_passes, prefix_passes, null_rule_fallbacks, strings_memo_hits, placement_report, _cert_failed,
+        _no_force_compact -- never"""
+
     def __init__(self, robot, param, params_std=None, coupling=False, tol_e=1e-6, tol_qr=qrd.TOL_QR, exchange=None,
                  chunk_samples=None, placement_trials=1, structural_zeros="every-pass", w_layout="dense", fuse=True, null_pivots=True,
                  row_blocks=None, native_tail=True):
@@ -92,9 +115,6 @@ class IdentificationPipeline:
         # fused pass of a single rank is ONE call (figh_chain_pass_fused: launches, copy, wait, check of the selection, tail).
         # False keeps the NumPy / LAPACK tail and one call per launch (tests, A/B runs).
         self.native_tail = bool(native_tail)
-        self._host_tail = None
-        self._strings_memo = None
-        self.strings_memo_hits = 0
         # row_blocks (ACTIVE JOINTS, examples/tiago/identification.py:148-187, :406-424): the dof indices (``act_idxv``) whose
         # row blocks carry measurements.  As in the script, the columns are eliminated on the norms of the FULL regressor
         # (every row block is walked for diag(W^T W)), but only the listed blocks are stored, and only they -- with their tau
@@ -102,20 +122,15 @@ class IdentificationPipeline:
         # row_blocks[i] (the script's tau[:, i]); out["rows"], sigma2_joint follow the list.  Joint-torque regressors of trees
         # of single-dof joints (the per-row-block TSQR), W resident.
         self.row_blocks = None if row_blocks is None else [int(b) for b in row_blocks]
-        self._own_handle = None
         # fuse (serial chains, W in the reference layout): from the second pass on K1 and the level-0 TSQR run as ONE launch
         # (figh_regressor_tsqr_fused) over the kept-column list of the previous pass -- every 64-row tile of W is factored
         # while it is still in LDS, W is written but not read back.  The list is verified against the norms the pass produces;
         # a pass whose kept set changed falls back to the two launches below (and learns the new list).
-        self.fuse = self._fuse_requested = bool(fuse)
+        self._fuse_requested = bool(fuse)
         # null_pivots: the TSQR launches of a pass run under the null-pivot rule (include/figh.h) and the pass is certified
         # afterwards; a pass that cannot be certified is repeated without the rule, which then stays off until the next
         # set_samples (null_rule_fallbacks counts those)
-        self.null_pivots = self._null_pivots_requested = bool(null_pivots)
-        self.null_rule_fallbacks = 0
-        self._cert_cache = None
-        self._fused_kept = None
-        self.fused_passes = 0
+        self._null_pivots_requested = bool(null_pivots)
         # structural_zeros = "once" (opt-in, joint-torque regressor of a tree kept in HBM): W is zero-filled when it is
         # allocated and the regressor kernel is told that the structural zeros are present (FIGH_FLAG_ZEROS_PRESENT) -- it
         # rewrites every entry that depends on q, v, a in every pass and leaves the zeros alone.  The default re-creates
@@ -139,15 +154,45 @@ class IdentificationPipeline:
         # same 4 GB depends on the physical pages behind them -- 0.68 or 0.82 ms per allocation, hipMemset moves with it
         # (0.60 / 0.63 ms), measured with an allocation probe since removed -- and the allocator offers no handle on that.
         self.placement_trials = max(1, int(placement_trials))
-        self.placement_report = None
         self.robot, self.param, self.coupling = robot, param, coupling
         self.tol_e, self.tol_qr = tol_e, tol_qr
         self.params_std = params_std if params_std is not None else robot.get_standard_parameters(param)
         self.names = list(self.params_std.keys())
         self.exchange = exchange or Exchange()
-        self.N = 0
-        self.d_q = self.d_v = self.d_a = self.d_tau = None
-        self.W = None
+        self._init_samples()
+        self._init_layout()
+        self.forget()
+        self._init_pass()
+        self._host_pack = self._d_kept_buf = self._d_block_tri = self._host_tail = self._own_handle = None
+        self._dc_colsq = self._dc_idx = self._dc_R = self._d_tailpack = self._host_tailpack = None
+        self._strings_memo = self._force_slot_mask = self._ancestors = None
+        self._scratch = {}
+        self.fused_passes = self.prefix_passes = self.null_rule_fallbacks = self.strings_memo_hits = 0
+        self.placement_report = self._cert_failed = None
+        self._no_force_compact = False  # (as found: set by run(wls=True) or a refused force / torque split, never reset)
+
+    def _init_samples(self, N=0, d_q=None, d_v=None, d_a=None, d_tau=None, in_flags=0, repack_ms=0.0):
+        self.N, self.d_q, self.d_v, self.d_a, self.d_tau = N, d_q, d_v, d_a, d_tau
+        self._in_flags, self.repack_ms = in_flags, repack_ms
+        self.fuse = self._fuse_requested
+        self.null_pivots = self._null_pivots_requested  # (a new sample set gets the rule -- and its certificate -- again)
+        self._force_compact_ok = False  # (set_samples decides)
+
+    def _init_layout(self):
+        self.W = self._compact = self._link_pos = self._d_link_pos = None
+        self._padded = self._zeros_once = self._wrench_split = self._tree_blocks = False
+        self._force_ld = self._sel_words = self._hint_blocks = self._padded_flags = 0
+        self._d_pack = self._d_colsq = self._d_sel = self._d_rows = self._d_R = None
+
+    def _init_pass(self):
+        self._have_block_tri, self._beta_later, self._cert_args = False, None, None
+
+    def _collective(self):
+        """Whether the exchange takes part in the pass.  The exchange is the user's object, so it is probed -- here only,
+        with the default of the passes.  (set_samples used to ask with the default False: the two differ only for an exchange
+        with world_size > 1 and no ``collective`` attribute, which no shipped or tested exchange is.)"""
+        ex = self.exchange
+        return getattr(ex, "collective", True)
 
     def _handle(self):
         """The device model of this pipeline: the robot's shared handle, or -- with ``row_blocks`` -- a private one that
@@ -179,17 +224,14 @@ class IdentificationPipeline:
         else:
             rps_in = rps
         tau_resident = tau is not None and (isinstance(tau, _lib.DeviceArray) or hasattr(tau, "ptr"))
-        if tau_resident:  # a device vector of the caller's (decimate_joint_blocks / reject_rows output): used as it is
-            if self.row_blocks is not None:
-                raise NotImplementedError("row_blocks: tau is re-laid per active dof on the host; pass a host array")
+        if tau_resident and self.row_blocks is not None:
+            raise NotImplementedError("row_blocks: tau is re-laid per active dof on the host; pass a host array")
+        if tau is not None:
+            if not tau_resident:  # (a device vector of the caller's -- decimate_joint_blocks / reject_rows output -- is used as it is)
+                tau = np.ascontiguousarray(tau, dtype=np.float64).reshape(-1)
             if int(tau.size) != rps_in * len(q):
                 raise ValueError("tau must have rows_per_sample * N = %d * %d = %d entries; got %d"
                                  % (rps_in, len(q), rps_in * len(q), int(tau.size)))
-        elif tau is not None:
-            tau = np.ascontiguousarray(tau, dtype=np.float64).reshape(-1)
-            if tau.shape[0] != rps_in * len(q):
-                raise ValueError("tau must have rows_per_sample * N = %d * %d = %d entries; got %d"
-                                 % (rps_in, len(q), rps_in * len(q), tau.shape[0]))
             if self.row_blocks is not None:  # block i of the caller's tau belongs to dof row_blocks[i]
                 full = np.zeros(rps * len(q))
                 for i, b in enumerate(self.row_blocks):
@@ -203,7 +245,7 @@ class IdentificationPipeline:
         # lane's values lie nq * 8 bytes from its neighbour's.  The three arrays are re-laid once per tile of 64 samples,
         # value-major (figh_repack_samples); K1' then reads one 512-byte line per value.  Chains keep the original arrays
         # (their kernel reads 48-byte runs per lane).
-        self._in_flags, self.repack_ms = 0, 0.0
+        in_flags, repack_ms = 0, 0.0
         m = self.robot.model
         if N > 0 and not (self._handle().is_chain() and mode == _lib.MODE_JOINT_TORQUE) and not self.coupling:
             import time
@@ -211,16 +253,19 @@ class IdentificationPipeline:
             t0 = time.perf_counter()
             blocked = [_lib.repack_samples(d, N, w) for d, w in ((d_q, m.nq), (d_v, m.nv), (d_a, m.nv))]
             _lib.synchronize()
-            self.repack_ms = 1e3 * (time.perf_counter() - t0)
+            repack_ms = 1e3 * (time.perf_counter() - t0)
             for d in (d_q, d_v, d_a):
                 if not any(d is b for b in borrowed):
                     d.free()
             d_q, d_v, d_a = blocked
-            self._in_flags = _lib.FLAG_BLOCKED_INPUTS
+            in_flags = _lib.FLAG_BLOCKED_INPUTS
             if self.chunk_samples:
                 self.chunk_samples = max(64, (int(self.chunk_samples) // 64) * 64)  # chunks start on tile boundaries
-        self.N, self.d_q, self.d_v, self.d_a, self.d_tau = N, d_q, d_v, d_a, d_tau
-        self.W = None
+        self._init_samples(N, d_q, d_v, d_a, d_tau, in_flags, repack_ms)  # (fuse and null_pivots are asked for again)
+        self._init_layout()  # (as found: W is dropped by assignment, NOT freed -- a caller may still hold pipe.W)
+        # (as found: of what was learnt only the certificate's sums go here; _fused_kept and _chunk_kept survive a new sample
+        # set, the five of _forget_columns wait for the allocation of the next W)
+        self._cert_cache = None
         # Fused launch: eligibility is decided again for every sample set (a set that was too small to fuse says nothing
         # about the next one), and under a collective exchange from a value all ranks agree on -- the fused launch needs at
         # least 4096 local samples, and ranks whose shards straddle that size must not take different paths through the
@@ -229,13 +274,10 @@ class IdentificationPipeline:
         # figh_tsqr_selected_wrench, refuses a shard with fewer than 16 nc / 3 samples (three row blocks of N rows each must
         # hold nc rows of 16-row tiles), and a rank-local fallback would re-run K1 and its collectives on that rank alone.
         # Whether ANY rank's shard is too small for it is agreed here, once per sample set.
-        self.fuse = self._fuse_requested
-        self.null_pivots = self._null_pivots_requested  # (a new sample set gets the rule -- and its certificate -- again)
-        self._cert_cache = None
         ncols_ref = self._handle().shape(mode, self._flags()[1])[1] if N > 0 else 0
         self._force_compact_ok = N >= 64 and 3 * N >= 16 * (ncols_ref + 1)
         ex = self.exchange
-        if getattr(ex, "collective", False) and ex.world_size > 1:
+        if self._collective() and ex.world_size > 1:
             flag = _lib.DeviceArray.from_host(np.array([0.0 if N >= 4096 else 1.0, 0.0 if self._force_compact_ok else 1.0]))
             agreed = np.asarray(ex.sum_columns(flag, 2)).reshape(-1)
             self.fuse = self.fuse and float(agreed[0]) == 0.0
@@ -246,7 +288,7 @@ class IdentificationPipeline:
         """(mode, flags, ft_mask) of this pipeline's regressor calls, including the layout of its input arrays."""
         from .tools.regressor import regressor_flags
         mode, flags, ft_mask = regressor_flags(self.param, self.coupling)
-        return mode, flags | getattr(self, "_in_flags", 0), ft_mask
+        return mode, flags | self._in_flags, ft_mask
 
     def _chunks(self):
         c = self.chunk_samples
@@ -281,22 +323,24 @@ class IdentificationPipeline:
                 self._build_chunk(lo, hi, Wc, None)
                 _lib.matvec(Wc.buf, rps * (hi - lo), Wc.ld, None, ncols, d_phi, d_t)
                 self._tau_chunk(lo, hi, rps, d_t, scatter=True)
-            if noise_std > 0.0:
-                tau = self.d_tau.to_host()
-                tau += np.random.default_rng(seed).standard_normal(tau.shape[0]) * noise_std
-                self.d_tau = _lib.DeviceArray.from_host(tau)
+            self.d_tau = self._with_noise(self.d_tau, noise_std, seed)
             return self.d_tau
         W, _ = build_regressor_device(self.robot, self.d_q, self.d_v, self.d_a, self.N, self.param, self.coupling,
                                       extra_flags=self._in_flags)
         d_phi = _lib.DeviceArray.from_host(np.ascontiguousarray(phi, dtype=np.float64))
         d_tau = _lib.DeviceArray((W.rows,), np.float64)
         _lib.matvec(W.buf, W.rows, W.ld, None, W.cols, d_phi, d_tau)
+        self.d_tau = d_tau = self._with_noise(d_tau, noise_std, seed)
+        W.buf.free()
+        return d_tau
+
+    @staticmethod
+    def _with_noise(d_tau, noise_std, seed):
+        """``d_tau`` itself, or a new device vector with N(0, noise_std) added on the host."""
         if noise_std > 0.0:
             tau = d_tau.to_host()
             tau += np.random.default_rng(seed).standard_normal(tau.shape[0]) * noise_std
             d_tau = _lib.DeviceArray.from_host(tau)
-        self.d_tau = d_tau
-        W.buf.free()
         return d_tau
 
     # ------------------------------------------------------------------ one pass of the hot path
@@ -307,7 +351,7 @@ class IdentificationPipeline:
         mode, flags, ft_mask = self._flags()
         dm = self.robot.device_model()
         rps, ncols = dm.shape(mode, flags)
-        if getattr(self, "_dc_colsq", None) is None or self._dc_colsq.size != ncols:
+        if self._dc_colsq is None or self._dc_colsq.size != ncols:
             cap = ncols + 1
             self._dc_colsq = _lib.DeviceArray((ncols,), np.float64)
             self._dc_idx = _lib.DeviceArray((cap,), np.int32)
@@ -319,7 +363,7 @@ class IdentificationPipeline:
         # list while diag(W^T W) of all columns is accumulated by the same regressor launches (figh_regressor_tsqr_norms), and
         # the set is verified against the norms afterwards -- the same speculation as run() makes with the column count.
         # (The norms decide on every rank from the all-reduced sums, so a mismatch sends all ranks to the two-pass form.)
-        cached = getattr(self, "_chunk_kept", None)
+        cached = self._chunk_kept
         if cached is not None and cached[0] == ncols:
             kept = cached[1]
             n = len(kept)
@@ -374,7 +418,7 @@ class IdentificationPipeline:
             if self.null_pivots and not out.get("null_rule_certified", True):
                 self.null_pivots = False
                 self.fused_passes = fused_before  # (counts the passes whose results were returned, not the discarded attempt)
-                self.null_rule_fallbacks = getattr(self, "null_rule_fallbacks", 0) + 1
+                self.null_rule_fallbacks += 1
                 # (kept for diagnostics, tools/cert_report.py: the bounds and the pivots of the pass that was not certified)
                 self._cert_failed = (self._cert_cache, out["absdiagR"].copy(), list(out["idx_base"]))
                 self._cert_cache = None
@@ -383,16 +427,16 @@ class IdentificationPipeline:
         return out
 
     def _run_once(self, strings, wls):
+        self._init_pass()
         if self._chunked():
             if wls:
                 raise NotImplementedError("wls=True needs the regressor resident in HBM (no chunk_samples)")
             return self._run_chunked(strings)
-        if wls and not getattr(self, "_no_force_compact", False):
+        if wls and not self._no_force_compact:
             # the weighted solve's second pass reads W as ONE matrix: from now on without the force-compact region
             self._no_force_compact = True
-            if getattr(self, "_force_ld", 0) and self.W is not None:
-                self.W.buf.free()
-                self.W = None
+            if self._force_ld and self.W is not None:
+                self._drop_resident()
         # (with the WLS the expression strings of the base parameters -- host work, 0.2 - 0.4 ms for TIAGo -- are built while
         # the weighted factorisation runs on the device)
         out = self._run_resident(strings and not wls, wls)
@@ -400,104 +444,107 @@ class IdentificationPipeline:
             self._wls(out, strings)
         return out
 
+    def _drop_resident(self):
+        """Free the resident W and forget its layout: the next pass allocates it and decides again."""
+        self.W.buf.free()
+        self._init_layout()
+
+    def _allocate_resident(self, handle, mode, flags, ft_mask):
+        """Allocate the resident W (once: every step reuses the HBM buffers) and decide its layout: the layout group's only writer."""
+        self._init_layout()
+        self._forget_columns()  # (what was learnt about the columns of the previous W goes with it)
+        rows_per_sample, ncols = handle.shape(mode, flags)
+        # W stays in HBM.  Chains: the reference's dense layout (the chain kernel streams one contiguous run per tile).
+        # Trees: the link-padded layout of figh_regressor_build_padded -- 16 columns per link, every (row, link)
+        # segment one 128-byte line -- which K1' writes at about twice the rate; the TSQR takes a column list anyway.
+        self._padded = not (handle.is_chain() and mode == _lib.MODE_JOINT_TORQUE) and not self.coupling
+        m = self.robot.model
+        wcols = 16 * (m.njoints - 1) if self._padded else ncols
+        # external wrench on a free-flyer root: links that cannot have a non-zero entry in any of the six row blocks
+        # (massless bodies, regressor.py:36-39; human model: 21 of 40) get no columns in the resident W -- their columns are
+        # eliminated whatever the samples (figh.h, FIGH_FLAG_LINK_COMPACT: 304 instead of 640 columns, which is what lets
+        # 1e7 human samples stay resident)
+        if self._padded and self.w_layout != "link-padded":
+            layout = _lib.regressor_link_layout(handle, mode, flags & 7, ft_mask)
+            if layout is not None and 0 < layout[1] < m.njoints - 1:
+                self._link_pos = layout[0].astype(np.int64)
+                self._d_link_pos = _lib.DeviceArray.from_host(layout[0])
+                wcols = 16 * layout[1]
+        # ... and the three FORCE row blocks in a region of their own, one 128-byte line per four links (a force row only
+        # has mx my mz m of every link: FIGH_FLAG_FORCE_COMPACT) -- 5/8 of the bytes of W, and the force rows' TSQR reads
+        # lines that are all payload.  Not with friction / inertia / offset columns; not for the weighted solve, whose second
+        # pass reads W as one matrix (run(wls=True) re-creates W without it).
+        if (self._padded and self.w_layout in ("dense", "block-compact") and not self._no_force_compact
+                and self._force_compact_ok):
+            self._force_ld = _lib.regressor_force_layout(handle, mode, flags & 7, ft_mask)
+        if (self.w_layout == "block-compact" and self._padded and mode == _lib.MODE_JOINT_TORQUE
+                and m.nv == m.njoints - 1 and self.N >= 64):
+            sizes = self._subtree_sizes()
+            j, k = np.nonzero(self._ancestor_matrix())  # depth-first numbering: the subtree of joint j + 1 is the links j .. j + size - 1
+            if not ((j <= k) & (k < j + sizes[j])).all():
+                raise RuntimeError("block-compact W needs depth-first joint numbering")
+            ld = 16 * sizes
+            if self.row_blocks is not None:  # blocks without measurements are not stored at all
+                keep = np.zeros(m.nv, dtype=bool)
+                keep[self.row_blocks] = True
+                ld = np.where(keep, ld, 0)
+            off = self.N * np.concatenate([[0], np.cumsum(ld)[:-1]])
+            self._compact = (off.astype(np.int64), ld.astype(np.int32))
+            self.W = GpuMatrix(_lib.DeviceArray((int(self.N * ld.sum()),), np.float64), rows_per_sample * self.N, wcols,
+                               wcols)
+            self.W.compact = self._compact
+        elif self._force_ld:
+            half = (rows_per_sample // 2) * self.N  # rows of the force region = rows of the torque region
+            self.W = GpuMatrix(_lib.DeviceArray((half * (self._force_ld + wcols),), np.float64), rows_per_sample * self.N,
+                               wcols, wcols)
+            self.W.force_ld = self._force_ld  # (rows [0, half): force region, ld force_ld; torque rows behind it, ld wcols)
+        else:
+            self.W = self._place_W(rows_per_sample * self.N, wcols, handle, mode, flags, ft_mask)
+        self.W.ref_cols = ncols
+        self._zeros_once = (self.structural_zeros == "once" and self._padded and mode == _lib.MODE_JOINT_TORQUE
+                            and self._compact is None)
+        if self._zeros_once:
+            _lib.check(_lib.load().figh_memset(self.W.buf.ptr, 0, self.W.rows * self.W.ld * 8))
+        # the flag word of figh_regressor_build_padded says what the layout decided
+        self._padded_flags = (flags | (_lib.FLAG_ZEROS_PRESENT if self._zeros_once else 0)
+                              | (_lib.FLAG_COMPACT_BLOCKS if self._compact is not None else 0)
+                              | (_lib.FLAG_LINK_COMPACT if self._link_pos is not None else 0)
+                              | (_lib.FLAG_FORCE_COMPACT if self._force_ld else 0))
+        cap = ncols + 1
+        # one buffer for everything that returns to the host: [colsq (ncols f64) | sel (2 + 2 ncols i32) | rows ((cap+1) cap f64)]
+        self._sel_words = (2 + 2 * ncols + 1) // 2
+        self._d_pack = _lib.DeviceArray((ncols + self._sel_words + (cap + 1) * cap,), np.float64)
+        self._d_colsq = _View(self._d_pack, 0)
+        self._d_sel = _View(self._d_pack, ncols * 8)
+        self._d_rows = _View(self._d_pack, (ncols + self._sel_words) * 8)
+        self._d_R = _lib.DeviceArray((cap * cap,), np.float64)
+        # joint-torque regressor of single-dof joints (regressor.py:45-87): the rows of joint j (row block j of N rows)
+        # only involve the links of j's subtree, which are numbered from j on -- the columns in front of 14 j are
+        # zeros written by K1; the device derives the per-tile form of that hint from its own column list
+        structured = mode == _lib.MODE_JOINT_TORQUE and m.nv == m.njoints - 1 and self.N >= 64
+        self._hint_blocks = m.nv if structured else 0
+        # external wrench on a free-flyer root: six row blocks, and in the three force blocks the rotational-inertia
+        # columns of every link are exact zeros -- figh_tsqr_selected_wrench factors those rows over the other
+        # columns only (the count of such kept columns is derived from the kept mask, like the column count)
+        from .model import JT_FREEFLYER
+        self._wrench_split = (mode == _lib.MODE_EXT_WRENCH and rows_per_sample == 6 and len(m.joints) > 1 and
+                              m.joints[1].jtype == JT_FREEFLYER and not self.coupling)
+        # joint-torque regressor of a tree of single-dof joints with more than 80 kept columns (TIAGo): per row block
+        # only the columns of the joint's subtree are non-zero -- figh_tsqr_selected_blocks (lists from the kept mask)
+        self._tree_blocks = bool(structured and self._padded)
+        if self._compact is not None and not self._tree_blocks:
+            raise RuntimeError("block-compact W needs the per-row-block TSQR")
+        if self.row_blocks is not None and not self._tree_blocks:
+            raise NotImplementedError("row_blocks needs the per-row-block TSQR: joint-torque regressor of a tree of "
+                                      "single-dof joints with at least 64 samples")
+
     def _run_resident(self, strings, wls):
         ex = self.exchange
-        # K1 (+ fused column norms)
         mode, flags, ft_mask = self._flags()
         handle = self._handle()
-        if self.W is None:  # HBM buffers are allocated once and reused by every step
-            self._kept_cache = None
-            self._n_expected = -1
-            self._mask_expected = None
-            rows_per_sample, ncols = handle.shape(mode, flags)
-            # W stays in HBM.  Chains: the reference's dense layout (the chain kernel streams one contiguous run per tile).
-            # Trees: the link-padded layout of figh_regressor_build_padded -- 16 columns per link, every (row, link)
-            # segment one 128-byte line -- which K1' writes at about twice the rate; the TSQR takes a column list anyway.
-            self._padded = not (handle.is_chain() and mode == _lib.MODE_JOINT_TORQUE) and not self.coupling
-            wcols = 16 * (self.robot.model.njoints - 1) if self._padded else ncols
-            m = self.robot.model
-            self._compact = None
-            # external wrench on a free-flyer root: links that cannot have a non-zero entry in any of the six row blocks
-            # (massless bodies, regressor.py:36-39; human model: 21 of 40) get no columns in the resident W -- their columns are
-            # eliminated whatever the samples (figh.h, FIGH_FLAG_LINK_COMPACT: 304 instead of 640 columns, which is what lets
-            # 1e7 human samples stay resident)
-            self._link_pos = self._d_link_pos = None
-            if self._padded and self.w_layout != "link-padded":
-                layout = _lib.regressor_link_layout(handle, mode, flags & 7, ft_mask)
-                if layout is not None and 0 < layout[1] < m.njoints - 1:
-                    self._link_pos = layout[0].astype(np.int64)
-                    self._d_link_pos = _lib.DeviceArray.from_host(layout[0])
-                    wcols = 16 * layout[1]
-            # ... and the three FORCE row blocks in a region of their own, one 128-byte line per four links (a force row only
-            # has mx my mz m of every link: FIGH_FLAG_FORCE_COMPACT) -- 5/8 of the bytes of W, and the force rows' TSQR reads
-            # lines that are all payload.  Not with friction / inertia / offset columns; not for the weighted solve, whose second
-            # pass reads W as one matrix (run(wls=True) re-creates W without it).
-            self._force_ld = 0
-            if (self._padded and self.w_layout in ("dense", "block-compact") and not getattr(self, "_no_force_compact", False)
-                    and getattr(self, "_force_compact_ok", self.N >= 64)):
-                self._force_ld = _lib.regressor_force_layout(handle, mode, flags & 7, ft_mask)
-            if (self.w_layout == "block-compact" and self._padded and mode == _lib.MODE_JOINT_TORQUE
-                    and m.nv == m.njoints - 1 and self.N >= 64):
-                sizes = self._subtree_sizes()
-                for k in range(m.nv):  # depth-first numbering: the subtree of joint j + 1 is the links j .. j + size - 1
-                    jid = k + 1
-                    while jid > 0:
-                        if not (jid - 1 <= k < jid - 1 + sizes[jid - 1]):
-                            raise RuntimeError("block-compact W needs depth-first joint numbering")
-                        jid = m.parents[jid]
-                ld = 16 * sizes
-                if self.row_blocks is not None:  # blocks without measurements are not stored at all
-                    keep = np.zeros(m.nv, dtype=bool)
-                    keep[self.row_blocks] = True
-                    ld = np.where(keep, ld, 0)
-                off = self.N * np.concatenate([[0], np.cumsum(ld)[:-1]])
-                self._compact = (off.astype(np.int64), ld.astype(np.int32))
-                self.W = GpuMatrix(_lib.DeviceArray((int(self.N * ld.sum()),), np.float64), rows_per_sample * self.N, wcols,
-                                   wcols)
-                self.W.compact = self._compact
-            elif self._force_ld:
-                half = (rows_per_sample // 2) * self.N  # rows of the force region = rows of the torque region
-                self.W = GpuMatrix(_lib.DeviceArray((half * (self._force_ld + wcols),), np.float64), rows_per_sample * self.N,
-                                   wcols, wcols)
-                self.W.force_ld = self._force_ld  # (rows [0, half): force region, ld force_ld; torque rows behind it, ld wcols)
-            else:
-                self.W = self._place_W(rows_per_sample * self.N, wcols, handle, mode, flags, ft_mask)
-            self.W.ref_cols = ncols
-            self._zeros_once = (self.structural_zeros == "once" and self._padded and mode == _lib.MODE_JOINT_TORQUE
-                                and self._compact is None)
-            if self._zeros_once:
-                _lib.check(_lib.load().figh_memset(self.W.buf.ptr, 0, self.W.rows * self.W.ld * 8))
-            cap = ncols + 1
-            # one buffer for everything that returns to the host: [colsq (ncols f64) | sel (2 + 2 ncols i32) | rows ((cap+1) cap f64)]
-            self._sel_words = (2 + 2 * ncols + 1) // 2
-            self._d_pack = _lib.DeviceArray((ncols + self._sel_words + (cap + 1) * cap,), np.float64)
-            self._d_colsq = _View(self._d_pack, 0)
-            self._d_sel = _View(self._d_pack, ncols * 8)
-            self._d_rows = _View(self._d_pack, (ncols + self._sel_words) * 8)
-            self._d_R = _lib.DeviceArray((cap * cap,), np.float64)
-            # joint-torque regressor of single-dof joints (regressor.py:45-87): the rows of joint j (row block j of N rows)
-            # only involve the links of j's subtree, which are numbered from j on -- the columns in front of 14 j are
-            # zeros written by K1; the device derives the per-tile form of that hint from its own column list
-            m = self.robot.model
-            structured = mode == _lib.MODE_JOINT_TORQUE and m.nv == m.njoints - 1 and self.N >= 64
-            self._hint_blocks = m.nv if structured else 0
-            # external wrench on a free-flyer root: six row blocks, and in the three force blocks the rotational-inertia
-            # columns of every link are exact zeros -- figh_tsqr_selected_wrench factors those rows over the other
-            # columns only (the count of such kept columns is derived from the kept mask, like the column count)
-            from .model import JT_FREEFLYER
-            self._wrench_split = (mode == _lib.MODE_EXT_WRENCH and rows_per_sample == 6 and len(m.joints) > 1 and
-                                  m.joints[1].jtype == JT_FREEFLYER and not self.coupling)
-            self._nf_expected = -1
-            # joint-torque regressor of a tree of single-dof joints with more than 80 kept columns (TIAGo): per row block
-            # only the columns of the joint's subtree are non-zero -- figh_tsqr_selected_blocks (lists from the kept mask)
-            self._tree_blocks = bool(structured and self._padded)
-            if self._compact is not None and not self._tree_blocks:
-                raise RuntimeError("block-compact W needs the per-row-block TSQR")
-            if self.row_blocks is not None and not self._tree_blocks:
-                raise NotImplementedError("row_blocks needs the per-row-block TSQR: joint-torque regressor of a tree of "
-                                          "single-dof joints with at least 64 samples")
-            self._block_cache = None
-        W, d_colsq, lib = self.W, self._d_colsq, _lib.load()
+        if self.W is None:
+            self._allocate_resident(handle, mode, flags, ft_mask)
+        W, d_colsq = self.W, self._d_colsq
         if (self.fuse and self._fused_kept is None and not self._padded and self.N >= 4096
                 and handle.is_chain() and mode == _lib.MODE_JOINT_TORQUE and not self.coupling):
             self._learn_kept_set(handle, mode, flags, ft_mask)
@@ -505,25 +552,23 @@ class IdentificationPipeline:
             out = self._run_fused(handle, flags, strings)
             if out is not None:
                 return out
+        # K1 (+ fused column norms)
         if self._padded:
-            _lib.regressor_build_padded(handle, mode, flags | (_lib.FLAG_ZEROS_PRESENT if self._zeros_once else 0)
-                                        | (_lib.FLAG_COMPACT_BLOCKS if self._compact is not None else 0)
-                                        | (_lib.FLAG_LINK_COMPACT if self._link_pos is not None else 0)
-                                        | (_lib.FLAG_FORCE_COMPACT if self._force_ld else 0), ft_mask,
-                                        self.N, self.d_q, self.d_v, self.d_a, W.buf, W.ld, d_colsq)
+            _lib.regressor_build_padded(handle, mode, self._padded_flags, ft_mask, self.N, self.d_q, self.d_v, self.d_a,
+                                        W.buf, W.ld, d_colsq)
         else:
             _lib.regressor_build(handle, mode, flags, ft_mask, self.N, self.d_q, self.d_v, self.d_a, W.buf, W.ld, d_colsq)
         ex.sum_columns_device(d_colsq, W.ref_cols)
         ncols, with_tau = W.ref_cols, self.d_tau is not None
         stride = 16 if self._padded else 14
-        split = getattr(self, "_wrench_split", False)
+        split, local = self._wrench_split, not self._collective()
+        tol_rank, d_out = (self.tol_qr, self._d_rows) if local else (-1.0, self._d_R)  # (collective: plain triangle, merged below)
         for attempt in range(4):
             n = self._n_expected
             nf = self._nf_expected if split else 0
             nc = n + (1 if with_tau else 0)
-            local = not getattr(ex, "collective", True)
             blocks = None
-            if getattr(self, "_tree_blocks", False) and (nc > 80 or self._compact is not None or self.row_blocks is not None):
+            if self._tree_blocks and (nc > 80 or self._compact is not None or self.row_blocks is not None):
                 blocks = self._block_lists(ncols, stride)
                 if blocks is None and self.row_blocks is not None and n > 0:
                     raise RuntimeError("row_blocks: no kept mask to build the column lists from")
@@ -532,9 +577,7 @@ class IdentificationPipeline:
             if split or self._link_pos is not None or self._force_ld:  # (nf = 0: the plain pass, through the entry that knows the layout)
                 try:
                     _lib.tsqr_selected_wrench(W.buf, W.rows, W.ld, d_colsq, ncols, self.tol_e, stride, n, nf, self.d_tau,
-                                              self.tol_qr if local else -1.0, self._d_sel,
-                                              self._d_rows if local else self._d_R, d_link_pos=self._d_link_pos,
-                                              ld_force=self._force_ld)
+                                              tol_rank, self._d_sel, d_out, d_link_pos=self._d_link_pos, ld_force=self._force_ld)
                 except _lib.FighError as e:
                     if not (self._force_ld and e.code == _lib.ERR_UNSUPPORTED):
                         raise
@@ -542,36 +585,26 @@ class IdentificationPipeline:
                     # the all-reduced norms, the same on every rank; shards too short for it were ruled out for all ranks in
                     # set_samples): this regressor is kept as one matrix from now on
                     self._no_force_compact = True
-                    self.W.buf.free()
-                    self.W = None
+                    self._drop_resident()
                     return self._run_resident(strings, wls)
             elif blocks is not None:
                 coff, cld = self._compact if self._compact is not None else (None, None)
                 _lib.tsqr_selected_blocks(W.buf, W.rows, W.ld, d_colsq, ncols, self.tol_e, stride, n, blocks[1],
-                                          blocks[4] if coff is not None else blocks[2], blocks[3], self.d_tau,
-                                          self.tol_qr if local else -1.0, self._d_sel, self._d_rows if local else self._d_R,
-                                          block_off=coff, block_ld=cld, d_block_tri=self._block_tri(wls, len(blocks[1]), nc))
+                                          blocks[4] if coff is not None else blocks[2], blocks[3], self.d_tau, tol_rank,
+                                          self._d_sel, d_out, block_off=coff, block_ld=cld,
+                                          d_block_tri=self._block_tri(wls, len(blocks[1]), nc))
             else:
                 _lib.tsqr_selected(W.buf, W.rows, W.ld, d_colsq, ncols, self.tol_e, stride, self._hint_blocks, n, self.d_tau,
-                                   self.tol_qr if local else -1.0, self._d_sel, self._d_rows if local else self._d_R)
+                                   tol_rank, self._d_sel, d_out)
             self._have_block_tri = bool(wls and blocks is not None and not split)
             if not local:
                 if n > 0:
                     d_stack, count = ex.stack_triangles(self._d_R, nc)
                     _lib.tsqr_merge_base(d_stack, count, nc, n, self.tol_qr, self._d_rows)
-            words = ncols + self._sel_words + ((nc + 1) * nc if n > 0 else 0)
-            # one page-locked landing buffer for the pass's results, reused by every step (everything run() returns is
-            # copied or derived from it before the next step overwrites it)
-            pin = getattr(self, "_host_pack", None)
-            if pin is None or pin.size < self._d_pack.size:
-                pin = self._host_pack = _lib.PinnedArray(self._d_pack.size)
-            host = pin.array[:words]
-            _lib.check(lib.figh_memcpy_d2h(host.ctypes.data, self._d_pack.ptr, host.nbytes))
-            sel = host[ncols:ncols + self._sel_words].view(np.int32)
+            norms, sel, mask_now, rows_k = self._fetch_pack(ncols, n, nc)
             nf_now = 0
             if split:  # kept columns that can be non-zero in force rows: slot >= 6 within the link
                 nf_now = int(np.count_nonzero(sel[2 + ncols:2 + 2 * ncols][self._force_slots(ncols)]))
-            mask_now = sel[2 + ncols:2 + 2 * ncols] != 0
             if int(sel[0]) == n and nf_now == nf and (blocks is None or np.array_equal(mask_now, blocks[0])):
                 break
             self._mask_expected = mask_now.copy()  # (the per-block column lists are built from the mask)
@@ -581,25 +614,12 @@ class IdentificationPipeline:
                 raise ValueError("every column of the regressor was eliminated")
         else:
             raise RuntimeError("the number of kept columns did not settle")
-        col_norm = host[:ncols].copy()
-        kept_mask = sel[2 + ncols:2 + 2 * ncols] != 0
-        cached = self._kept_cache
-        if cached is not None and np.array_equal(cached[0], kept_mask):
-            _, idx_e, params_r = cached  # same columns as in the previous pass: the derived lists are reused
-            idx_e, params_r = list(idx_e), list(params_r)  # (the caller owns what run() returns)
-        else:
-            idx_e = np.flatnonzero(~kept_mask).tolist()
-            params_r = [self.names[i] for i in np.flatnonzero(kept_mask).tolist()]
-            self._kept_cache = (kept_mask.copy(), list(idx_e), list(params_r))
-        rows_k = host[ncols + self._sel_words:].reshape(nc + 1, nc)
+        col_norm = norms.copy()
+        kept_mask = mask_now
+        idx_e, params_r = self._kept_lists(kept_mask)
         if self.fuse and not self._padded and self._compact is None and (
                 self._fused_kept is None or not np.array_equal(self._fused_kept[0], kept_mask)):
-            kept = np.flatnonzero(kept_mask).astype(np.int32)
-            buf = getattr(self, "_d_kept_buf", None)
-            if buf is None or buf.size < ncols:
-                buf = self._d_kept_buf = _lib.DeviceArray((ncols,), np.int32)
-            _lib.check(lib.figh_memcpy_h2d(buf.ptr, kept.ctypes.data, kept.nbytes))
-            self._fused_kept = (kept_mask.copy(), buf, len(kept))
+            self._remember_fused_kept(kept_mask, ncols)
         rows_mine = W.rows if self.row_blocks is None else len(self.row_blocks) * self.N
         return self._finish(rows_k, n, nc, params_r, idx_e, col_norm, with_tau, rows_mine * ex.world_size, strings,
                             defer_beta=wls and with_tau)
@@ -609,13 +629,45 @@ class IdentificationPipeline:
         ``run()`` is a FIRST pass again -- what a script that calls the reference's functions once pays
         (examples/ur10/identification.py:71-83) -- with the HBM buffers still allocated.  bench.py times it as
         ``ms_first_pass``."""
-        self._fused_kept = None
-        self._kept_cache = None
+        self._forget_columns()
+        # (as found: null_pivots and fuse stay as a pass left them, _strings_memo and _no_force_compact are kept)
+        self._fused_kept = self._chunk_kept = self._cert_cache = None
+
+    def _forget_columns(self):
+        """The part of forget() that goes with a resident W: its kept columns, their counts and per-block lists."""
+        self._kept_cache = self._mask_expected = self._block_cache = None
         self._n_expected = self._nf_expected = -1
-        self._mask_expected = None
-        self._block_cache = None
-        self._chunk_kept = None
-        self._cert_cache = None
+
+    def _fetch_pack(self, ncols, n, nc):
+        """[column norms | selection | rows] by one copy into the landing buffer -> (column norms, selection words, kept mask,
+        rows_k of n > 0 kept columns), views of that buffer except the mask."""
+        words = ncols + self._sel_words + ((nc + 1) * nc if n > 0 else 0)
+        host = self._landing().array[:words]
+        _lib.check(_lib.load().figh_memcpy_d2h(host.ctypes.data, self._d_pack.ptr, host.nbytes))
+        sel = host[ncols:ncols + self._sel_words].view(np.int32)
+        rows_k = host[ncols + self._sel_words:].reshape(nc + 1, nc) if n > 0 else None
+        return host[:ncols], sel, sel[2 + ncols:2 + 2 * ncols] != 0, rows_k
+
+    def _landing(self):
+        """The page-locked landing buffer of the results, reused by every step (run() copies what it returns out of it)."""
+        pin = self._host_pack = _grown(self._host_pack, self._d_pack.size, _lib.PinnedArray)
+        return pin
+
+    def _kept_lists(self, mask):
+        """(idx_e, params_r) of a kept mask, reused while the columns stay the same (fresh copies: the caller owns them)."""
+        cached = self._kept_cache
+        if cached is None or not np.array_equal(cached[0], mask):
+            idx_e = np.flatnonzero(~mask).tolist()
+            params_r = [self.names[i] for i in np.flatnonzero(mask).tolist()]
+            cached = self._kept_cache = (mask.copy(), idx_e, params_r)
+        return list(cached[1]), list(cached[2])
+
+    def _remember_fused_kept(self, mask, ncols):
+        """The kept set of the next fused launch: (mask, column list in a grow-only device buffer, count)."""
+        kept = np.flatnonzero(mask).astype(np.int32)
+        buf = self._d_kept_buf = _grown(self._d_kept_buf, ncols, lambda k: _lib.DeviceArray((k,), np.int32))
+        _lib.check(_lib.load().figh_memcpy_h2d(buf.ptr, kept.ctypes.data, kept.nbytes))
+        self._fused_kept = (mask.copy(), buf, len(kept))
 
     PREFIX_SAMPLES = 4096
 
@@ -636,24 +688,19 @@ class IdentificationPipeline:
         mask = sel[2 + W.ref_cols:] != 0
         if not mask.any():
             return
-        kept = np.flatnonzero(mask).astype(np.int32)
-        buf = getattr(self, "_d_kept_buf", None)
-        if buf is None or buf.size < W.ref_cols:  # (allocated once: hipMalloc synchronises the device)
-            buf = self._d_kept_buf = _lib.DeviceArray((W.ref_cols,), np.int32)
-        _lib.check(_lib.load().figh_memcpy_h2d(buf.ptr, kept.ctypes.data, kept.nbytes))
-        self._fused_kept = (mask.copy(), buf, len(kept))
-        self.prefix_passes = getattr(self, "prefix_passes", 0) + 1
+        self._remember_fused_kept(mask, W.ref_cols)
+        self.prefix_passes += 1
 
     def _run_fused(self, handle, flags, strings):
         """One pass with K1 and the level-0 TSQR in one launch over the kept-column list of the previous pass
         (figh_regressor_tsqr_fused).  Returns None -- the caller takes the two-launch path -- when the shape is not supported
         or the kept set turned out to be different."""
-        ex, lib, W = self.exchange, _lib.load(), self.W
+        ex, W = self.exchange, self.W
         self._have_block_tri = False
         mask, d_kept, n = self._fused_kept
         ncols, with_tau = W.ref_cols, self.d_tau is not None
         nc = n + (1 if with_tau else 0)
-        local = not getattr(ex, "collective", True)
+        local = not self._collective()
         if local and self.native_tail and nc <= 80:
             return self._run_fused_native(handle, flags, strings, mask, d_kept, n, nc, with_tau)
         if not _lib.regressor_tsqr_fused(handle, flags, self.N, self.d_q, self.d_v, self.d_a, W.buf, W.ld, self._d_colsq,
@@ -666,37 +713,21 @@ class IdentificationPipeline:
         if not local:
             d_stack, count = ex.stack_triangles(self._d_R, nc)
             _lib.tsqr_merge_base(d_stack, count, nc, n, self.tol_qr, self._d_rows)
-        words = ncols + self._sel_words + (nc + 1) * nc
-        pin = getattr(self, "_host_pack", None)
-        if pin is None or pin.size < self._d_pack.size:
-            pin = self._host_pack = _lib.PinnedArray(self._d_pack.size)
-        host = pin.array[:words]
-        _lib.check(lib.figh_memcpy_d2h(host.ctypes.data, self._d_pack.ptr, host.nbytes))
-        sel = host[ncols:ncols + self._sel_words].view(np.int32)
-        mask_now = sel[2 + ncols:2 + 2 * ncols] != 0
+        norms, _, mask_now, rows_k = self._fetch_pack(ncols, n, nc)
         if not np.array_equal(mask_now, mask):
             self._fused_kept = None  # the kept set changed: the two-launch path learns the new one
             return None
         self.fused_passes += 1
         self._n_expected = n
-        cached = self._kept_cache
-        if cached is not None and np.array_equal(cached[0], mask):
-            idx_e, params_r = list(cached[1]), list(cached[2])
-        else:
-            idx_e = np.flatnonzero(~mask).tolist()
-            params_r = [self.names[i] for i in np.flatnonzero(mask).tolist()]
-            self._kept_cache = (mask.copy(), list(idx_e), list(params_r))
-        rows_k = host[ncols + self._sel_words:].reshape(nc + 1, nc)
-        return self._finish(rows_k, n, nc, params_r, idx_e, host[:ncols].copy(), with_tau, W.rows * ex.world_size, strings)
+        idx_e, params_r = self._kept_lists(mask)
+        return self._finish(rows_k, n, nc, params_r, idx_e, norms.copy(), with_tau, W.rows * ex.world_size, strings)
 
     def _run_fused_native(self, handle, flags, strings, mask, d_kept, n, nc, with_tau):
         """_run_fused for a single rank in one call (figh_chain_pass_fused): the launches, the copy of the pack, the wait, the
         check of the selection and the host tail, without a return to Python in between."""
         ex, W = self.exchange, self.W
         ncols = W.ref_cols
-        pin = getattr(self, "_host_pack", None)
-        if pin is None or pin.size < self._d_pack.size:
-            pin = self._host_pack = _lib.PinnedArray(self._d_pack.size)
+        pin = self._landing()
         total_rows = W.rows * ex.world_size
         tail = self._tail_args(n, with_tau, total_rows)
         ok = _lib.chain_pass_fused(handle, flags, self.N, self.d_q, self.d_v, self.d_a, W.buf, W.ld, d_kept, n, self.d_tau,
@@ -710,13 +741,7 @@ class IdentificationPipeline:
             return None
         self.fused_passes += 1
         self._n_expected = n
-        cached = self._kept_cache
-        if cached is not None and np.array_equal(cached[0], mask):
-            idx_e, params_r = list(cached[1]), list(cached[2])
-        else:
-            idx_e = np.flatnonzero(~mask).tolist()
-            params_r = [self.names[i] for i in np.flatnonzero(mask).tolist()]
-            self._kept_cache = (mask.copy(), list(idx_e), list(params_r))
+        idx_e, params_r = self._kept_lists(mask)
         out = self._native_out(tail, n, params_r, idx_e, pin.array[:ncols].copy(), with_tau, total_rows, strings)
         # EMPIRICAL, mechanism not understood (profiles/chain_pass_tail_ab.txt, section 5): during the first forty or so passes of
         # a process, passes that follow each other without the NumPy / LAPACK tail start on a 149 us grid (steps of 1337 / 1487 /
@@ -788,15 +813,13 @@ class IdentificationPipeline:
         if not wls:
             return None
         need = (nblocks + 2) * nc * nc  # (the compact stack is at most nblocks nc rows + nc + 1 rows of slack)
-        buf = getattr(self, "_d_block_tri", None)
-        if buf is None or buf.size < need:
-            buf = self._d_block_tri = _lib.DeviceArray((need,), np.float64)
+        buf = self._d_block_tri = _grown(self._d_block_tri, need, lambda k: _lib.DeviceArray((k,), np.float64))
         return buf
 
     def _sb(self, name, count, dtype=np.float64):
         """A device scratch buffer of this pipeline, kept from pass to pass (figh_malloc / figh_free synchronise the stream:
         six of them per weighted solve were 0.3 ms of a 14 ms TIAGo step)."""
-        pool = self.__dict__.setdefault("_scratch", {})
+        pool = self._scratch
         buf = pool.get(name)
         if buf is None or buf.size != int(count) or buf.dtype != np.dtype(dtype):
             if buf is not None:
@@ -841,7 +864,7 @@ class IdentificationPipeline:
         _lib.check(_lib.load().figh_memcpy_h2d(d_r2.ptr + 8 * nblocks, _rows.ctypes.data, 8))
         d_Rw = self._sb("wls_Rw", (nb_par + 1) * (nb_par + 1))
         kept = np.flatnonzero(self._kept_cache[0])
-        if getattr(self, "_have_block_tri", False):
+        if self._have_block_tri:
             # the compact stack of the pass: block j holds its n_j + 1 triangle rows over the kept columns + tau
             tri = self._d_block_tri
             counts = np.asarray(self._block_cache[1], dtype=np.int64) + 1
@@ -871,7 +894,7 @@ class IdentificationPipeline:
             sig2 = r2[:nblocks] / r2[nblocks]
             _lib.tsqr(W.buf, W.rows, W.ld, d_cols, nb_par, self.d_tau, 1.0 / np.sqrt(sig2), d_Rw)
             source = "second pass over W"
-        if getattr(ex, "collective", True) and ex.world_size > 1:
+        if self._collective() and ex.world_size > 1:
             d_stack, count = ex.stack_triangles(d_Rw, nb_par + 1)
             d_one = self._sb("wls_one", (nb_par + 1) * (nb_par + 1))
             _lib.tsqr_merge(d_stack, count, nb_par + 1, d_one)
@@ -895,7 +918,7 @@ class IdentificationPipeline:
 
     def _finish_beta(self, out):
         """The regrouping coefficients _finish left for later (``defer_beta``): beta = R1^-1 R2, rounded (qrdecomposition.py:244)."""
-        later = getattr(self, "_beta_later", None)
+        later = self._beta_later
         if later is None or out.get("beta") is not None:
             return
         R1, R2, _, _ = later
@@ -908,21 +931,13 @@ class IdentificationPipeline:
         (joint j + 1) gets the kept inertial columns of the links in that joint's subtree and the kept Ia / fv / fs / off
         columns of its own link -- everything else in the block is a structural zero of the regressor
         (regressor.py:45-87).  None while no mask is known."""
-        mask = getattr(self, "_mask_expected", None)
+        mask = self._mask_expected
         if mask is None or len(mask) != ncols:
             return None
         cached = self._block_cache
         if cached is not None and np.array_equal(cached[0], mask):
             return cached
-        m = self.robot.model
-        nb = m.nv
-        parents = list(m.parents)
-        anc = np.zeros((nb, nb), dtype=bool)  # anc[j, k]: joint j + 1 is joint k + 1 or one of its ancestors
-        for k in range(nb):
-            jid = k + 1
-            while jid > 0:
-                anc[jid - 1, k] = True
-                jid = parents[jid]
+        nb, anc = self.robot.model.nv, self._ancestor_matrix()
         kept = np.flatnonzero(mask)
         link, slot = kept // 14, kept % 14
         counts, cols, pos, ccols = [], [], [], []
@@ -946,20 +961,25 @@ class IdentificationPipeline:
 
     def _subtree_sizes(self):
         """Links in the subtree of every joint (depth-first numbering: the subtree of joint j + 1 is links j .. j + size - 1)."""
-        m = self.robot.model
-        nb = m.nv
-        parents = list(m.parents)
-        size = np.zeros(nb, dtype=np.int64)
-        for k in range(nb):
-            jid = k + 1
-            while jid > 0:
-                size[jid - 1] += 1
-                jid = parents[jid]
-        return size
+        return self._ancestor_matrix().sum(axis=1, dtype=np.int64)
+
+    def _ancestor_matrix(self):
+        """anc[j, k]: joint j + 1 is joint k + 1 or one of its ancestors (a property of the model: walked once)."""
+        anc = self._ancestors
+        if anc is None:
+            m = self.robot.model
+            parents = list(m.parents)
+            anc = self._ancestors = np.zeros((m.nv, m.nv), dtype=bool)
+            for k in range(m.nv):
+                jid = k + 1
+                while jid > 0:
+                    anc[jid - 1, k] = True
+                    jid = parents[jid]
+        return anc
 
     def _force_slots(self, ncols):
         """Mask over the reference's columns: slot >= 6 within a link (mx my mz m Ia fv fs off)."""
-        m = getattr(self, "_force_slot_mask", None)
+        m = self._force_slot_mask
         if m is None or len(m) != ncols:
             m = self._force_slot_mask = (np.arange(ncols) % 14) >= 6
         return m
@@ -967,19 +987,19 @@ class IdentificationPipeline:
     def device_columns(self, ref_cols):
         """Column indices of the HBM-resident ``self.W`` that hold the reference's columns ``ref_cols`` (trees keep W
         link-padded: 16 columns per link, reference column c at 16 (c // 14) + c % 14)."""
-        if getattr(self, "_compact", None) is not None:
+        if self._compact is not None:
             raise ValueError("block-compact W has no global column numbering: row block j is its own N x 16 |subtree_j| "
                              "matrix (pipe.W.compact = (element offsets, leading dimensions))")
         c = np.asarray(ref_cols, dtype=np.int64)
-        if getattr(self, "_force_ld", 0):
+        if self._force_ld:
             raise ValueError("force-compact W is two matrices (force rows: pipe.W.force_ld columns, torque rows behind them): "
                              "no single column numbering; IdentificationPipeline(w_layout='link-compact') keeps one")
-        if getattr(self, "_link_pos", None) is not None:  # link-compact: only links with entries have a segment
+        if self._link_pos is not None:  # link-compact: only links with entries have a segment
             pos = self._link_pos[c // 14]
             if (pos < 0).any():
                 raise ValueError("link-compact W holds no columns for links without entries (structural zeros)")
             return pos * 16 + c % 14
-        return (c // 14) * 16 + c % 14 if getattr(self, "_padded", False) else c
+        return (c // 14) * 16 + c % 14 if self._padded else c
 
     def _place_W(self, rows, cols, handle, mode, flags, ft_mask):
         """Allocate W; with ``placement_trials`` > 1 keep the candidate allocation on which K1 runs fastest."""
@@ -1014,13 +1034,9 @@ class IdentificationPipeline:
         """Stack of plain triangles in HBM (one per rank) -> results: reduction, rank decision and regrouped factorisation
         on the device (figh_tsqr_merge_base), one copy back."""
         lib = _lib.load()
-        pack = getattr(self, "_d_tailpack", None)
-        if pack is None or pack.size < (nc + 1) * nc:
-            pack = self._d_tailpack = _lib.DeviceArray(((nc + 1) * nc,), np.float64)
+        pack = self._d_tailpack = _grown(self._d_tailpack, (nc + 1) * nc, lambda k: _lib.DeviceArray((k,), np.float64))
         _lib.tsqr_merge_base(d_stack, count, nc, n, self.tol_qr, pack)
-        pin = getattr(self, "_host_tailpack", None)
-        if pin is None or pin.size < (nc + 1) * nc:
-            pin = self._host_tailpack = _lib.PinnedArray((nc + 1) * nc)
+        pin = self._host_tailpack = _grown(self._host_tailpack, (nc + 1) * nc, _lib.PinnedArray)
         host = pin.array[:(nc + 1) * nc]
         _lib.check(lib.figh_memcpy_d2h(host.ctypes.data, pack.ptr, host.nbytes))
         return self._finish(host.reshape(nc + 1, nc), n, nc, params_r, idx_e, col_norm, with_tau, total_rows, strings)
@@ -1056,7 +1072,7 @@ class IdentificationPipeline:
             # than of the samples); the margins are this pass's own pivots
             from ._host import null_rule_bounds
             key = (n, base.tobytes())
-            cache = getattr(self, "_cert_cache", None)
+            cache = self._cert_cache
             if cache is None or cache[0] != key:
                 with _single_threaded_blas(n):
                     cache = self._cert_cache = (key, null_rule_bounds(np.triu(R1), R2))
