@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # FIGH_LIB_PATH: another build of the same ABI (same-box A/B of kernel variants); default is the in-tree library
 LIB_PATH = os.environ.get("FIGH_LIB_PATH") or os.path.join(_HERE, "libfigh.so")
 
-ABI_VERSION = 113  # include/figh.h FIGH_ABI_VERSION: load() refuses a library of another ABI
+ABI_VERSION = 114  # include/figh.h FIGH_ABI_VERSION: load() refuses a library of another ABI
 
 FIGH_OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_ALLOC, ERR_UNSUPPORTED, ERR_COMM = -1, -2, -3, -4, -5
@@ -126,6 +126,9 @@ SIGNATURES = {
     "figh_excitation_constraints": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, _c_int32_p, _c_int32_p, C.c_int,
                                               _c_int32_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                               C.c_void_p, C.c_int64]),
+    "figh_collision_distances": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, _c_int32_p, C.c_void_p, C.c_int64, C.c_int,
+                                           _c_int32_p, _c_int32_p, _c_double_p, _c_double_p, C.c_int, _c_int32_p, C.c_double,
+                                           C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "figh_kinematic_regressor": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, _c_double_p, C.c_int,
                                            _c_double_p, _c_int32_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
                                            C.c_int64, C.c_void_p, C.c_void_p]),
@@ -561,6 +564,26 @@ def excitation_constraints(model, B, n_per, act_idxq, act_idxv, idx_waypoints, q
 
 def _ptr(x):
     return x.ptr if hasattr(x, "ptr") else x
+
+
+def collision_distances(model, B, n_per, idx, q_ptr, ldq, kind, parent, placement, dims, pairs, tol, max_iter, out_ptr, ld_b,
+                        witness_ptr=None, status_ptr=None):
+    """figh_collision_distances on raw device addresses: out[b ld_b + i n_pairs + p] for the samples ``idx`` (None: every
+    sample) of B trajectories of n_per configurations; the geometry table and the pair list are host arrays (figh.h)."""
+    kind, parent, pairs = _i32(kind).reshape(-1), _i32(parent).reshape(-1), _i32(pairs).reshape(-1)
+    placement, dims = _f64(placement).reshape(-1), _f64(dims).reshape(-1)
+    n_geom = len(kind)
+    if len(parent) != n_geom or len(placement) != 12 * n_geom or len(dims) != 3 * n_geom or len(pairs) % 2:
+        raise ValueError("collision_distances: %d kinds, %d parents, %d placement and %d dimension entries, %d pair entries"
+                         % (n_geom, len(parent), len(placement), len(dims), len(pairs)))
+    iw = _i32(idx).reshape(-1) if idx is not None else None
+    check(load().figh_collision_distances(model.handle if model is not None else None, B, n_per,
+                                          len(iw) if iw is not None else 0,
+                                          iw.ctypes.data_as(_c_int32_p) if iw is not None else None, _ptr(q_ptr), ldq, n_geom,
+                                          kind.ctypes.data_as(_c_int32_p), parent.ctypes.data_as(_c_int32_p),
+                                          placement.ctypes.data_as(_c_double_p), dims.ctypes.data_as(_c_double_p),
+                                          len(pairs) // 2, pairs.ctypes.data_as(_c_int32_p), float(tol), int(max_iter),
+                                          _ptr(out_ptr), ld_b, _ptr(witness_ptr), _ptr(status_ptr)))
 
 
 def kinematic_regressor(model, N, q_ptr, ldq, end_joint, end_placement, start_joint, start_placement, support, meas_mask,

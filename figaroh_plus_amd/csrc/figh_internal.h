@@ -124,6 +124,7 @@ enum WorkspaceSlot {
     kWsDesignPartials,      // figh_design_gram: the workgroups' tile partials
     kWsDesignGram,          // figh_design_gram: M ahead of its copy to the host
     kWsDesignFactor,        // figh_design_scores: the packed, padded Cholesky factor
+    kWsCollisionIdx,        // figh_collision_distances: the sample indices
     kWorkspaceSlots
 };
 

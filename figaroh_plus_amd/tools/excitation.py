@@ -221,7 +221,9 @@ class CubicSpline:
     / ``get_full_config`` / ``check_cfg_constraints``.  Host arrays in, host arrays out through the NumPy mirror above;
     ``get_full_config(..., device_resident=True)`` returns three ``GpuMatrix`` written by ``figh_spline_sample``.  The time of
     a sample is capped at the end of its segment: where rounding puts the last sample behind the last time point ndcurves
-    raises, this class evaluates the end of the last segment.  Plotting, waypoint pools and collisions are not mirrored."""
+    raises, this class evaluates the end of the last segment.  Plotting and waypoint pools are not mirrored; the self-collision
+    distances of the constraint vector come from ``tools.robotcollisions`` (:func:`constraint_vector`,
+    :func:`constraints_batch` and :func:`evaluate_waypoints_batch` with ``collision=``)."""
 
     def __init__(self, robot, num_waypoints, active_joints, soft_lim=0):
         self.robot = robot
@@ -391,10 +393,11 @@ def waypoint_sample_indices(t, tps):
     return np.flatnonzero(np.isin(t, np.asarray(tps, dtype=np.float64).reshape(-1)[1:]))
 
 
-def constraint_vector(spline, t_f, p_f, v_f, tau, tps):
-    """get_constraints_all_samples (examples/tiago/optimal_trajectory.py:156-174, :185-187) of one trajectory on host arrays,
-    without the collision distances: positions of the active joints at the waypoints, their velocities and efforts at every
-    sample, concatenated."""
+def constraint_vector(spline, t_f, p_f, v_f, tau, tps, collision=None):
+    """get_constraints_all_samples (examples/tiago/optimal_trajectory.py:156-188) of one trajectory on host arrays: positions
+    of the active joints at the waypoints, their velocities and efforts at every sample and, with a ``CollisionWrapper`` as
+    ``collision``, the distances of its pairs at the waypoint samples (waypoint-major, pair-minor: the reference's np.append
+    over idx_waypoints of getDistances(), :176-182), concatenated.  ``collision=None``: the first three parts."""
     Ns = len(p_f)
     idx = waypoint_sample_indices(t_f, tps)
     q_c = np.asarray(p_f)[idx, :][:, spline.act_idxq]
@@ -403,13 +406,54 @@ def constraint_vector(spline, t_f, p_f, v_f, tau, tps):
     tau_c = np.zeros((Ns, len(spline.act_idxv)))
     for k, j in enumerate(spline.act_idxv):
         tau_c[:, k] = tau[j * Ns:(j + 1) * Ns]
-    return np.concatenate((q_c, v_c, tau_c), axis=None)
+    if collision is None:
+        return np.concatenate((q_c, v_c, tau_c), axis=None)
+    dist_all = np.zeros(0)
+    if len(idx):
+        collision.computeCollisions(np.asarray(p_f)[idx, :])
+        dist_all = collision.getDistances().reshape(-1)
+    return np.concatenate((q_c, v_c, tau_c, dist_all), axis=None)
 
 
-def constraints_batch(spline, batch, tau, tps):
+def collision_distances_batch(robot, batch, idx, geom_model=None, device_resident=False, tol=None, max_iter=None):
+    """(B, n_idx n_pairs): the self-collision distances of every trajectory of a :class:`TrajectoryBatch` at its samples
+    ``idx`` (None: every sample), waypoint-major and pair-minor per trajectory -- the reference's np.append over
+    idx_waypoints of getDistances() (examples/tiago/optimal_trajectory.py:176-182) -- in one ``figh_collision_distances``
+    launch on the resident configurations.  ``device_resident``: the result stays on the device, a ``GpuMatrix``."""
+    from ..device import GpuMatrix
+    from . import robotcollisions as rc
+    gm = robot.geom_model if geom_model is None else geom_model
+    n_pairs = len(gm.collisionPairs)
+    n_idx = batch.n_per if idx is None else len(idx)
+    out = GpuMatrix.empty(batch.B, n_idx * n_pairs)
+    if n_idx * n_pairs:
+        rc.collision_distances_device(robot, gm, batch.q.ptr, batch.q.ld, batch.B, batch.n_per, idx, out.ptr, out.ld,
+                                      rc.DEFAULT_TOL if tol is None else tol,
+                                      rc.DEFAULT_MAX_ITER if max_iter is None else max_iter)
+    return out if device_resident else out.buf.to_host().reshape(batch.B, n_idx * n_pairs)
+
+
+def constraint_bounds(spline, n_wps, Ns, n_pairs=0, margin=0.01):
+    """``(cl, cu)`` of get_constr_value (examples/tiago/optimal_trajectory.py:202-243) as lists: the position limits of the
+    active joints per waypoint behind the first, their velocity and effort limits per sample, and ``margin`` (1 cm) and 2e19
+    ("no limit") for the ``n_pairs`` collision distances of each of those waypoints."""
+    cl, cu = [], []
+    for lower, upper, reps in ((spline.lower_q, spline.upper_q, n_wps - 1), (spline.lower_dq, spline.upper_dq, Ns),
+                               (spline.lower_effort, spline.upper_effort, Ns)):
+        for _ in range(reps):
+            cl.extend(lower)
+            cu.extend(upper)
+    cl += [margin] * n_pairs * (n_wps - 1)
+    cu += [2 * 1e19] * n_pairs * (n_wps - 1)
+    return cl, cu
+
+
+def constraints_batch(spline, batch, tau, tps, collision=None):
     """(B, n_con) host array, row b = :func:`constraint_vector` of trajectory b, gathered on the device
     (``figh_excitation_constraints``) and brought back in one copy.  ``tau``: what ``calc_torque_batch(robot, batch,
-    dict(param, device_resident=True))`` returns (the batched layout)."""
+    dict(param, device_resident=True))`` returns (the batched layout).  With a ``CollisionWrapper`` as ``collision`` the rows
+    are (n_wps - 1) n_pairs longer: ``figh_collision_distances`` writes the distances at the waypoint samples straight into
+    the tail of the rows of the same buffer -- one output buffer, one download."""
     if not isinstance(tau, _lib.DeviceArray):
         tau = _lib.DeviceArray.from_host(np.ascontiguousarray(tau, dtype=np.float64).reshape(-1))
     nv = spline.rmodel.nv
@@ -418,21 +462,36 @@ def constraints_batch(spline, batch, tau, tps):
     idx = waypoint_sample_indices(batch.t, tps)
     n_act = len(spline.act_idxv)
     n_con = len(idx) * n_act + 2 * batch.n_per * n_act
-    out = _lib.DeviceArray((batch.B * n_con,), np.float64)
+    if collision is None:
+        out = _lib.DeviceArray((batch.B * n_con,), np.float64)
+        _lib.excitation_constraints(spline.robot.device_model(), batch.B, batch.n_per, spline.act_idxq, spline.act_idxv, idx,
+                                    batch.q.ptr, batch.q.ld, batch.v.ptr, batch.v.ld, tau, out.ptr, n_con)
+        return out.to_host().reshape(batch.B, n_con)
+    from . import robotcollisions as rc
+    n_dist = len(idx) * len(collision.gmodel.collisionPairs)
+    ld = n_con + n_dist
+    out = _lib.DeviceArray((batch.B * ld,), np.float64)
     _lib.excitation_constraints(spline.robot.device_model(), batch.B, batch.n_per, spline.act_idxq, spline.act_idxv, idx,
-                                batch.q.ptr, batch.q.ld, batch.v.ptr, batch.v.ld, tau, out.ptr, n_con)
-    return out.to_host().reshape(batch.B, n_con)
+                                batch.q.ptr, batch.q.ld, batch.v.ptr, batch.v.ld, tau, out.ptr, ld)
+    if n_dist:
+        rc.collision_distances_device(spline.robot, collision.gmodel, batch.q.ptr, batch.q.ld, batch.B, batch.n_per, idx,
+                                      out.ptr + 8 * n_con, ld, collision.tol, collision.max_iter)
+    return out.to_host().reshape(batch.B, ld)
 
 
 def evaluate_waypoints_batch(robot, spline, freq, tps, X_batch, vel_wps, acc_wps, wp_init, param, idx_e, idx_base,
-                             R_stack=None):
+                             R_stack=None, collision=None):
     """``(conds, constraints)``: ``objective`` and ``constraints`` of the script's Ipopt problem
     (examples/tiago/optimal_trajectory.py:100-188, :296-327) at the B rows of ``X_batch`` -- the points of one finite-difference
     gradient or Jacobian.  Waypoints go up, B condition numbers (through B r x r triangles) and the (B, n_con) constraint
-    vectors come back; the samples, v and tau never leave the device."""
+    vectors come back; the samples, v and tau never leave the device.  ``collision``: a ``CollisionWrapper`` whose pairs'
+    distances at the waypoint samples are the fourth part of every constraint vector (:func:`constraints_batch`); None: the
+    first three parts."""
     n_act, n_wps = spline.dim_q
     wps = waypoints_from_search_variables(X_batch, wp_init, n_wps, n_act)
     batch = spline_batch(spline, freq, tps, wps, vel_wps, acc_wps)
     conds = objective_cond_batch(robot, batch, param, idx_e, idx_base, R_stack)
     d_tau = calc_torque_batch(robot, batch, dict(param, device_resident=True))
-    return conds, constraints_batch(spline, batch, d_tau, tps)
+    if collision is None:
+        return conds, constraints_batch(spline, batch, d_tau, tps)
+    return conds, constraints_batch(spline, batch, d_tau, tps, collision)

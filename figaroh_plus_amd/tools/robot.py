@@ -12,6 +12,7 @@ import os
 import numpy as np
 
 from ..model import Model, build_model_from_urdf
+from .robotcollisions import GeometryModel
 
 _MODELS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "models")
 
@@ -37,6 +38,7 @@ class Robot:
         self.q0 = self.model.neutral()
         self.v0 = np.zeros(self.model.nv)
         self.nq, self.nv = self.model.nq, self.model.nv
+        self.geom_model = GeometryModel()  # collision objects and pairs (tools/robotcollisions.py), empty by default
         self._handle = None
 
     @classmethod

@@ -91,7 +91,7 @@ typedef struct figh_model_s *figh_model_t;
  * (round 5 did so for figh_tsqr_selected_wrench / figh_regressor_build_padded without a bump: a library of the older ABI
  * accepts the longer argument list under cdecl and silently ignores the new arguments).  figaroh_plus_amd/_lib.py refuses a
  * library -- in-tree or FIGH_LIB_PATH -- whose figh_version() differs from the value it was written against. */
-#define FIGH_ABI_VERSION 113
+#define FIGH_ABI_VERSION 114
 int figh_version(void);
 const char *figh_last_error(void);
 int figh_device_count(int *count);
@@ -562,6 +562,43 @@ int figh_excitation_constraints(figh_model_t model, int64_t B, int64_t n_per, in
                                 const int32_t *h_act_idxv, int n_idx, const int32_t *h_idx_waypoints, const double *d_q,
                                 int64_t ldq, const double *d_v, int64_t ldv, const double *d_tau, double *d_out,
                                 int64_t ld_out);
+
+/* figh_collision_distances: the fourth part of that constraint vector, the self-collision distances of the simplified
+ * collision model (examples/tiago/optimal_trajectory.py:176-186: CollisionWrapper.computeCollisions + getDistances,
+ * src/figaroh/tools/robotcollisions.py:62-72, :108-113, over the objects and pairs of
+ * examples/tiago/utils/simplified_colission_model.py:55-180), for samples of B trajectories of n_per configurations
+ * (d_q: B n_per x nq, leading dimension ldq).  h_idx: n_idx sample indices in [0, n_per) at which to evaluate; NULL: every
+ * sample (n_idx is ignored and counts as n_per below).
+ * The geometry table, launch-uniform HOST arrays over n_geom <= FIGH_COLLISION_MAX_GEOMETRIES objects: h_kind (FIGH_GEOM_*),
+ * h_parent (the joint the object is fixed to, 0: the universe), h_placement (12 doubles each: R row-major, then p, object to
+ * joint coordinates) and h_dims (3 doubles each, as hpp-fcl's constructors take them: box x y z full sides; cylinder radius,
+ * full length along z; sphere radius; capsule radius, full length of its axis segment; unused entries 0).  h_pairs: n_pairs
+ * <= FIGH_COLLISION_MAX_PAIRS pairs (first, second) of object ids.  The caps are what the kernel-argument block holds.
+ * Convention: a shape is a convex core and a radius r (box, cylinder: their own core, r = 0; sphere: its centre; capsule: its
+ * axis segment) and d = dist(core_A, core_B) - r_A - r_B -- the Euclidean distance of separated shapes (hpp-fcl's
+ * min_distance), minus the penetration depth of rounded shapes in shallow overlap, and exactly -(r_A + r_B) with status
+ * FIGH_COLLISION_CORES_INTERSECT when the cores intersect (hpp-fcl runs EPA there; not mirrored).  GJK in fp64 on the world
+ * placements oM_parent . placement, one query per lane (csrc/figh_collision.hip, tools/robotcollisions.py): a query stops
+ * with FIGH_COLLISION_OK when |v| - v.w / |v| <= tol (v the closest point of the simplex, w the new support point of
+ * core_A - core_B: v.w / |v| <= dist <= |v|), and after max_iter support evaluations with FIGH_COLLISION_ITERATION_CAP,
+ * when |v| is still an upper bound.
+ * d_out[b ld_b + i n_pairs + p]: the distance of pair p at sample i of trajectory b -- two strides, so that the distances
+ * can land behind the other three parts of a constraint row (d_out: the address of that tail, ld_b: the row stride);
+ * nothing else of the buffer is written.  d_witness (6 doubles per query (b n_idx + i) n_pairs + p: the witness points on
+ * core A and core B, world frame) and d_status (int32 per query: the status, the number of support evaluations in the
+ * upper half) may each be NULL.  Plain stores, no atomics: two calls give the same bits.
+ * FIGH_ERR_INVALID (nothing launched, figh_last_error says why): n_geom or n_pairs outside [1, cap], max_iter outside
+ * [1, 1024], tol <= 0 or not finite, an unknown kind, a parent that is no joint, a pair naming an object that does not exist
+ * (or one object twice), an index outside [0, n_per), ld_b < n_idx n_pairs, ldq < nq.  Without a HIP device:
+ * FIGH_ERR_NO_DEVICE, before any argument is looked at. */
+#define FIGH_COLLISION_MAX_GEOMETRIES 16
+#define FIGH_COLLISION_MAX_PAIRS 64
+enum { FIGH_GEOM_BOX = 0, FIGH_GEOM_CYLINDER = 1, FIGH_GEOM_SPHERE = 2, FIGH_GEOM_CAPSULE = 3 };
+enum { FIGH_COLLISION_OK = 0, FIGH_COLLISION_CORES_INTERSECT = 1, FIGH_COLLISION_ITERATION_CAP = 2 };
+int figh_collision_distances(figh_model_t model, int64_t B, int64_t n_per, int n_idx, const int32_t *h_idx,
+                             const double *d_q, int64_t ldq, int n_geom, const int32_t *h_kind, const int32_t *h_parent,
+                             const double *h_placement, const double *h_dims, int n_pairs, const int32_t *h_pairs, double tol,
+                             int max_iter, double *d_out, int64_t ld_b, double *d_witness, int32_t *d_status);
 
 /* ------------------------------------------------------------------ geometric calibration
  * The kinematic regressor and the updated forward kinematics of src/figaroh/calibration/calibration_tools.py, over
