@@ -148,6 +148,32 @@ def normwise_backward_err(R, G):
     return float(np.abs(R.T @ R - G).max() / np.abs(G).max())
 
 
+# ------------------------------------------------------------------------------------ the null-pivot rule's column bound
+TOL_QR = 1e-8          # qrdecomposition.py:205-221: |R_kk| > tol_qr decides the base columns
+NULL_TOL = TOL_QR / 64  # the rule's threshold per level-0 triangle (_lib.null_pivots)
+
+
+def null_bound(G, rows, pieces):
+    """(Shared by test_qr_structured_graded.py and test_streamed_columnwise.py.)  Column-wise bound with the null-pivot rule
+    on: TOL_BACKWARD + (tol_qr / 64) sqrt(T) (|a_i| + |a_j|) / (|a_i| |a_j|), T from _host.null_rule_triangles."""
+    from figaroh_plus_amd._host import null_rule_triangles
+    nrm = col_norms(G)
+    nrm = np.where(nrm > 0, nrm, 1.0)
+    T = null_rule_triangles(rows, pieces)
+    return TOL_BACKWARD + NULL_TOL * np.sqrt(T) * (nrm[:, None] + nrm[None, :]) / np.outer(nrm, nrm), nrm
+
+
+def null_rule_check(R, G, rows, pieces, base, n, tag, record_property, rule):
+    assert np.flatnonzero(np.abs(np.diag(R))[:n] > TOL_QR).tolist() == base, "%s: base set differs" % tag
+    bound, nrm = null_bound(G, rows, pieces)
+    if not rule:
+        bound = np.full_like(bound, TOL_BACKWARD)
+    Rl = np.asarray(np.triu(R), dtype=np.longdouble)
+    E = np.abs(Rl.T @ Rl - np.asarray(G, dtype=np.longdouble)) / np.outer(nrm, nrm).astype(np.longdouble)
+    record_property("%s:backward_over_bound" % tag, "%.3e" % float((E / bound).max()))
+    assert (E <= bound).all(), "%s: column-wise backward error above the bound" % tag
+
+
 # ------------------------------------------------------------------------------------ structured generators (wrench, blocks)
 def make_dependent(rng, X, s, n, lo, same_class=None):
     """(Shared by test_qr_graded.py and the structured tests.)  Make every third column k < n (k % 3 == 2) of ``X`` (last axis = columns) an exact combination, with coefficients

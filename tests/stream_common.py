@@ -1,0 +1,268 @@
+"""Host side of the streamed-TSQR tests (tests/test_streamed_plan_host.py, tests/test_streamed_columnwise.py).
+
+``stream_plan`` mirrors, from the source, every decision ``regressor_tsqr_impl`` (csrc/figh_stream.hip) takes on the host
+before and inside its chunk loop; ``CASES`` is the table of calls the GPU tests make, and the host test asserts through the
+mirror that the table reaches every branch of that loop.  Nothing here needs a device.
+
+The mirror leaves out the one device-dependent term: ``chain_wgs`` is also capped at ``tsqr_level0_capacity(nc) - 1``
+(compute units x occupancy of the blocked kernel).  Every case keeps ``rps cs / rsplit / (8 nc)`` at a few workgroups, far
+below any compute-unit count, so the cap never binds (asserted in the host test: at most MAX_CHAIN_WGS).
+"""
+import functools
+from collections import namedtuple
+
+import numpy as np
+
+MODE_JOINT_TORQUE, MODE_EXT_WRENCH = 0, 1  # include/figh.h (figaroh_plus_amd/_lib.py)
+FLAG_TX40, FLAG_BLOCKED_INPUTS = 8, 512
+
+MAX_CHUNKS = 6          # the level-0 stack is nchunks x capacity x nc^2 doubles
+MAX_GRAM_WORK = 3.0e8   # rows x nc^2: multiply-adds of the long-double Gram (about 9e7 per second)
+MAX_CHAIN_WGS = 16      # rps cs / rsplit / (8 nc) of every case: far below cu_count x occupancy - 1
+
+Plan = namedtuple("Plan", "n nc cs nchunks last padded link_compact hinted chained split nf ncf chain_wgs level0_launches "
+                          "pieces")
+
+
+def default_chunk(rps, ncols):
+    c = int(2.0e9 / (8.0 * rps * ncols))
+    c = (c // 64) * 64
+    return max(c, 64)
+
+
+def stream_plan(rps, ncols, nlinks, is_chain, mode, flags, free_flyer, single_dof, cols, with_tau, weighted, N,
+                chunk_samples, live_links):
+    """The decisions of regressor_tsqr_impl for one call.  ``cols``: the caller's list (None: all columns);
+    ``live_links``: per link whether the link-compact layout gives it a segment (tree_link_positions), or None where that
+    layout does not apply.  Returns a Plan; ``hinted`` is one bool per chunk, ``link_compact`` True, False or "fallback"."""
+    cols = list(range(ncols)) if cols is None else [int(c) for c in cols]
+    n = len(cols)
+    nc = n + (1 if with_tau else 0)
+    if chunk_samples == 0:
+        chunk_samples = default_chunk(rps, ncols)
+    cs = min(chunk_samples, N)
+    nchunks = -(-N // cs)
+    sizes = [min(cs, N - lo) for lo in range(0, N, cs)]
+    tx40 = bool(flags & FLAG_TX40)
+    padded = not (is_chain and mode == MODE_JOINT_TORQUE) and not tx40
+    link_compact = False
+    if padded and live_links is not None and mode == MODE_EXT_WRENCH and free_flyer and not tx40:
+        nlive = sum(bool(x) for x in live_links)
+        if 0 < nlive < nlinks:
+            ok = all(0 <= c and c // 14 < nlinks and live_links[c // 14] for c in cols)
+            link_compact = True if ok else "fallback"
+    is_sorted = all(cols[i - 1] < cols[i] for i in range(1, n))
+    hint = mode == MODE_JOINT_TORQUE and single_dof and nc <= 80 and cs >= 64 and is_sorted
+    hinted = [bool(hint and s >= 64) for s in sizes]
+    chained = nc > 80 and nchunks > 1
+    nf = 0
+    if (mode == MODE_EXT_WRENCH and rps == 6 and free_flyer and not tx40 and not weighted and nc > 80
+            and 3 * cs >= 16 * nc):
+        nf = sum(c % 14 >= 6 for c in cols)
+        if nf >= n:
+            nf = 0
+    split = nf > 0
+    ncf = nf + (1 if with_tau else 0)
+    rsplit = 2 if split else 1
+    chain_wgs = max(1, rps * cs // rsplit // (8 * nc)) if chained else 0
+    return Plan(n, nc, cs, nchunks, sizes[-1], padded, link_compact, hinted, chained, split, nf, ncf, chain_wgs,
+                nchunks * (2 if split else 1), rps * nchunks)
+
+
+# --------------------------------------------------------------------------------------------------------------- models
+GOLDEN = {"ur10": "cfg2_ur10", "tx40": "cfg1_tx40", "tiago": "cfg3_tiago", "talos": "cfg4_talos", "human": "cfg5_human"}
+Facts = namedtuple("Facts", "rps ncols nlinks is_chain free_flyer single_dof massive")
+
+
+def tree_param(wrench=False, force_torque=("All",), extras=False):
+    """The param dict of a random tree (regressor_exact.base_param)."""
+    import regressor_exact as rx
+    return rx.base_param(wrench=wrench, force_torque=force_torque, friction=extras, inertia=extras, offset=extras)
+
+
+@functools.lru_cache(maxsize=None)
+def robot_of(model):
+    """A shipped model, or a random tree built as test_regressor_entrywise.test_tape_kernel_random_trees builds it
+    ('fork': fixed base, 'fork-ff' / 'binary15-ff': under a free-flyer root)."""
+    if model in GOLDEN:
+        from figaroh_plus_amd.tools.robot import Robot
+        return Robot.from_flat(model)
+    from test_regressor_entrywise import _tree
+    shape, _, ff = model.partition("-")
+    return _tree(shape, ff == "ff")[0]
+
+
+def golden_of(model):
+    from conftest import Golden
+    return Golden(GOLDEN[model])
+
+
+def facts(model, param, coupling=False):
+    """What the plan needs to know of (model, param), from the flattened model alone."""
+    flat = robot_of(model).model.to_flat()
+    nj = int(flat["njoints"])
+    jtype, parents = np.asarray(flat["jtype"]), np.asarray(flat["parents"])
+    nv = int(flat["nv"])
+    jt = bool(param["is_joint_torques"])
+    is_chain = nj - 1 <= 8 and all(int(jtype[i]) == 0 and int(parents[i]) == i - 1 for i in range(1, nj))
+    massive = [float(flat["mass"][i]) != 0.0 for i in range(1, nj)]
+    return Facts(nv if jt else 6, 14 * (nj - 1) + (3 if coupling else 0), nj - 1, is_chain, nj > 1 and int(jtype[1]) == 3,
+                 nv == nj - 1, massive)
+
+
+def call_flags(param, coupling, extra):
+    from figaroh_plus_amd.tools.regressor import regressor_flags
+    mode, flags, ft = regressor_flags(param, coupling)
+    return mode, flags | extra, ft
+
+
+def live_links(f, mode, flags, ft_mask):
+    """tree_link_positions (csrc/figh_regressor_tree.hip): a link has a segment when it has mass and a wrench component
+    is selected, or with any of the friction / actuator-inertia / offset flags; None where the layout does not apply."""
+    if mode != MODE_EXT_WRENCH or not f.free_flyer or (flags & FLAG_TX40):
+        return None
+    extras = bool(flags & 7)
+    return [bool((m and (ft_mask & 63)) or extras) for m in f.massive]
+
+
+# --------------------------------------------------------------------------------------------------------- column lists
+def _kept(model):
+    g = golden_of(model)
+    f = facts(model, g.param, g.coupling)
+    gone = set(int(x) for x in g["idx_e"])
+    return np.array([c for c in range(f.ncols) if c not in gone], dtype=np.int32)
+
+
+def _base(model):
+    """The golden base columns in W's own numbering (idx_base counts within the kept list), ascending."""
+    return np.sort(_kept(model)[np.asarray(golden_of(model)["idx_base"], dtype=np.int64)]).astype(np.int32)
+
+
+def _slots(links, slots):
+    return np.array(sorted(14 * l + s for l in links for s in slots), dtype=np.int32)
+
+
+def _fork_fixed_78():
+    """78 columns of the fixed-base fork (all flags on), ascending, none of the massless link 3."""
+    rng = np.random.default_rng(78)
+    cand = np.array([c for c in range(14 * 13) if c // 14 != 3])
+    return np.sort(rng.choice(cand, 78, replace=False)).astype(np.int32)
+
+
+def _fork_ff_live():
+    return [l for l, m in enumerate(facts("fork-ff", tree_param(True)).massive) if m]
+
+
+RECIPES = {
+    # golden kept lists: every column the golden elimination keeps (UR10 49, TX40 76 with the coupling columns)
+    "kept": lambda model: _kept(model),
+    # golden base columns (UR10 36, human 164): full column rank, well conditioned after equilibration
+    "base": lambda model: _base(model),
+    # TIAGo: its 179 base columns, and every other one of them (90)
+    "tiago_base": lambda model: _base("tiago"),
+    "tiago_base_half": lambda model: _base("tiago")[::2],
+    # TALOS: every fourth kept column (83: inertia and force-capable slots of all links)
+    "talos_fourth": lambda model: _kept("talos")[::4],
+    "fork_78": lambda model: _fork_fixed_78(),
+    "fork_78_shuffled": lambda model: np.random.default_rng(5).permutation(_fork_fixed_78()).astype(np.int32),
+    # floating fork, 12 links with mass: their 48 force-capable columns (slots 6 .. 9) and 48 inertia columns (0 .. 3)
+    "fork_ff_mix": lambda model: _slots(_fork_ff_live(), (0, 1, 2, 3, 6, 7, 8, 9)),
+    # ... and its full kept list: slots 0 .. 9 of the links with mass (120 columns, the dependent ones among them)
+    "fork_ff_kept": lambda model: _slots(_fork_ff_live(), range(10)),
+    # floating binary tree with friction, actuator inertia and offsets: 86 force-capable columns and 10 inertia columns
+    "binary_ff_wide_force": lambda model: np.sort(np.r_[_slots(range(10), range(6, 14)), _slots([10], range(6, 12)),
+                                                        _slots(range(10), [0])]).astype(np.int32),
+    # ... and force-capable columns only (nf == n: no split)
+    "binary_ff_force_only": lambda model: _slots(range(16), range(6, 14))[:90],
+    # human: the first 120 kept columns (links with mass only), and the same plus the inertia columns of massless link 1
+    "human_live": lambda model: _kept("human")[:120],
+    "human_dead_link": lambda model: np.sort(np.r_[_kept("human")[:120], np.arange(14, 20)]).astype(np.int32),
+}
+
+
+def column_list(case):
+    return np.ascontiguousarray(RECIPES[case.recipe](case.model), dtype=np.int32)
+
+
+# ---------------------------------------------------------------------------------------------------------------- cases
+Case = namedtuple("Case", "id model param recipe with_tau weights N chunk flags")
+_G = {m: None for m in GOLDEN}
+
+
+def _gp(model):
+    """(param, coupling) of a golden config."""
+    if _G[model] is None:
+        g = golden_of(model)
+        _G[model] = (dict(g.param), bool(g.coupling))
+    return _G[model]
+
+
+def case_param(case):
+    """(param dict, coupling) of a case: 'golden', or the keyword set of tree_param."""
+    if case.param == "golden":
+        return _gp(case.model)
+    return tree_param(**dict(case.param)), False
+
+
+_FF = (("wrench", True),)
+_FF_X = (("wrench", True), ("extras", True))
+_FF_T = (("wrench", True), ("force_torque", ("Mx", "My", "Mz")))
+_FIX_X = (("extras", True),)
+_POW2_24 = tuple(2.0 ** ((3 * j) % 5 - 2) for j in range(24))  # one weight per joint of TIAGo
+_POW2_6 = (1.0, 0.5, 2.0, 4.0, 0.25, 1.0)                    # one per wrench component
+
+CASES = [
+    # a. chunk shapes: UR10 + tau (nc = 50, chain kernel, dense chunk W, hinted), TX40 with coupling (nc = 77)
+    Case("a_even", "ur10", "golden", "kept", True, None, 768, 256, 0),
+    Case("a_ragged", "ur10", "golden", "kept", True, None, 612, 256, 0),
+    Case("a_last37", "ur10", "golden", "kept", True, None, 549, 256, 0),
+    Case("a_last1", "ur10", "golden", "kept", True, None, 513, 256, 0),
+    Case("a_chunk150", "ur10", "golden", "kept", True, None, 400, 150, 0),
+    Case("a_chunk50", "ur10", "golden", "kept", True, None, 230, 50, 0),
+    Case("a_one_chunk", "ur10", "golden", "kept", True, None, 300, 1000, 0),
+    Case("a_base_ragged", "ur10", "golden", "base", True, None, 612, 256, 0),
+    Case("a_tx40_ragged", "tx40", "golden", "kept", True, None, 612, 256, 0),
+    Case("a_tx40_last1", "tx40", "golden", "kept", True, None, 513, 256, 0),
+    # b. hinted tree, register-tile kernel, link-padded chunk W
+    Case("b_sorted", "fork", _FIX_X, "fork_78", True, None, 356, 128, 0),
+    Case("b_unsorted", "fork", _FIX_X, "fork_78_shuffled", True, None, 356, 128, 0),
+    # c. chained launches with several workgroups (TIAGo: 24 rows per sample; TALOS: a chain under the split's threshold)
+    Case("c_narrow_ragged", "tiago", "golden", "tiago_base_half", True, None, 375, 128, 0),
+    Case("c_narrow_last1", "tiago", "golden", "tiago_base_half", True, None, 257, 128, 0),
+    Case("c_medium_ragged", "tiago", "golden", "tiago_base", True, None, 375, 128, 0),
+    Case("c_medium_last1", "tiago", "golden", "tiago_base", True, None, 257, 128, 0),
+    Case("c_weighted", "tiago", "golden", "tiago_base_half", True, _POW2_24, 375, 128, 0),
+    Case("c_talos", "talos", "golden", "talos_fourth", True, None, 612, 256, 0),
+    # d. the force / torque split (cs = 576 >= 16 * 97 / 3)
+    Case("d_even", "fork-ff", _FF, "fork_ff_mix", True, None, 1728, 576, 0),
+    Case("d_ragged", "fork-ff", _FF, "fork_ff_mix", True, None, 1252, 576, 0),
+    Case("d_last1_no_tau", "fork-ff", _FF, "fork_ff_mix", False, None, 1153, 576, 0),
+    Case("d_wide_force", "binary15-ff", _FF_X, "binary_ff_wide_force", True, None, 1252, 576, 0),
+    Case("d_torque_only", "fork-ff", _FF_T, "fork_ff_mix", True, None, 1252, 576, 0),
+    Case("d_off_force_only", "binary15-ff", _FF_X, "binary_ff_force_only", True, None, 1252, 576, 0),
+    Case("d_off_weights", "fork-ff", _FF, "fork_ff_mix", True, _POW2_6, 1252, 576, 0),
+    Case("d_human_base", "human", "golden", "base", True, None, 996, 896, 0),
+    Case("d_gram", "fork-ff", _FF, "fork_ff_mix", True, None, 1728, 576, 0),
+    # e. link-compact chunk W and its fallback (human: 21 of 40 links without mass), chained
+    Case("e_compact", "human", "golden", "human_live", True, None, 612, 256, 0),
+    Case("e_fallback", "human", "golden", "human_dead_link", True, None, 612, 256, 0),
+    # f. tile-blocked inputs, chunked (the sample-major call of the same case is b_sorted's)
+    Case("f_blocked", "fork", _FIX_X, "fork_78", True, None, 356, 128, FLAG_BLOCKED_INPUTS),
+    Case("f_blocked_chain", "tiago", "golden", "tiago_base_half", True, None, 375, 128, FLAG_BLOCKED_INPUTS),
+    # g. the null-pivot rule over chunks: lists with real dependent columns
+    Case("g_ur10", "ur10", "golden", "kept", True, None, 612, 256, 0),
+    Case("g_split", "fork-ff", _FF, "fork_ff_kept", True, None, 1508, 704, 0),
+]
+CASE = {c.id: c for c in CASES}
+# the entry a case calls when it is not figh_regressor_tsqr
+ENTRY = {"a_last37": "norms", "c_narrow_last1": "norms", "d_ragged": "norms", "e_compact": "norms", "d_gram": "gram"}
+FULL_RANK = {"a_base_ragged", "d_human_base"}  # cases whose long-double Cholesky factor is a valid reference (diagonal metric)
+DEAD_COLUMNS = {"e_fallback": list(range(14, 20))}  # listed columns that are exact zeros (reference numbering)
+
+
+def case_plan(case):
+    param, coupling = case_param(case)
+    f = facts(case.model, param, coupling)
+    mode, flags, ft = call_flags(param, coupling, case.flags)
+    return stream_plan(f.rps, f.ncols, f.nlinks, f.is_chain, mode, flags, f.free_flyer, f.single_dof, column_list(case),
+                       case.with_tau, case.weights is not None, case.N, case.chunk, live_links(f, mode, flags, ft))

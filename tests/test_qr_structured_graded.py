@@ -307,23 +307,7 @@ def test_blocks_graded_exact_dependencies(lib, case, profile, record_property):
 
 
 # ---------------------------------------------------------------------------------------------------- null-pivot rule
-def _null_bound(G, rows, pieces):
-    from figaroh_plus_amd._host import null_rule_triangles
-    nrm = qg.col_norms(G)
-    nrm = np.where(nrm > 0, nrm, 1.0)
-    T = null_rule_triangles(rows, pieces)
-    return TOL_BACKWARD + NULL_TOL * np.sqrt(T) * (nrm[:, None] + nrm[None, :]) / np.outer(nrm, nrm), nrm
-
-
-def _null_rule_check(R, G, rows, pieces, base, n, tag, record_property, rule):
-    assert np.flatnonzero(np.abs(np.diag(R))[:n] > TOL_QR).tolist() == base, "%s: base set differs" % tag
-    bound, nrm = _null_bound(G, rows, pieces)
-    if not rule:
-        bound = np.full_like(bound, TOL_BACKWARD)
-    Rl = np.asarray(np.triu(R), dtype=np.longdouble)
-    E = np.abs(Rl.T @ Rl - np.asarray(G, dtype=np.longdouble)) / np.outer(nrm, nrm).astype(np.longdouble)
-    record_property("%s:backward_over_bound" % tag, "%.3e" % float((E / bound).max()))
-    assert (E <= bound).all(), "%s: column-wise backward error above the bound" % tag
+_null_bound, _null_rule_check = qg.null_bound, qg.null_rule_check  # (shared with test_streamed_columnwise.py)
 
 
 @pytest.mark.parametrize("case", ["human", "talos"])
