@@ -86,7 +86,7 @@ enum WorkspaceSlot {
     kWsLevel0TriOrWrench,   // level-0 triangles: tsqr_level0 without a caller buffer, figh_fused.hip, the wrench torque stack
     kWsHintFirst,           // tile_hint: the first columns of the hint blocks
     kWsChunkW,              // W of a streamed chunk (figh_regressor_colsq, regressor_tsqr_impl) or of the whole batch
-    kWsChunkNormsOrCols,    // figh_regressor_colsq's chunk norms; the padded column list of the streamed and batched TSQR
+    kWsChunkNormsOrCols,    // figh_regressor_colsq's chunk norms; ChunkW::columns: the padded column list (streamed, batched TSQR)
     kWsChunkTau,            // regressor_tsqr_impl: tau of a chunk
     kWsChunkStack,          // level-0 triangles of all chunks (regressor_tsqr_impl) or trajectories (batch)
     kWsGramR,               // figh_regressor_gram: R
@@ -101,7 +101,7 @@ enum WorkspaceSlot {
     kWsChunkNormsFused,     // regressor_tsqr_impl: diag(W^T W) of a chunk
     kWsForceCols,           // the force rows' column list: figh_tsqr_selected_wrench, regressor_tsqr_impl
     kWsForceOrBlockTri,     // level-0 triangles: the wrench entry's force rows, the blocks entry's plain blocks
-    kWsForceOrBlockR,       // the force rows' triangle (wrench entry, regressor_tsqr_impl); the blocks entry's block triangles
+    kWsForceOrBlockR,       // append_force_triangle's Rf (wrench entry, regressor_tsqr_impl); the blocks entry's block triangles
     kWsChunkForceStack,     // regressor_tsqr_impl: the force rows' level-0 triangles of all chunks
     kWsBlockStack,          // figh_tsqr_selected_blocks: the compact stack when the caller keeps none
     kWsCompactCounts,       // figh_compact_rows: kept rows per group
@@ -114,7 +114,7 @@ enum WorkspaceSlot {
     kWsStacksBlk,           // reduce_wide_stacks: Rblk of its grouped launches
     kWsStacksJobs,          // reduce_wide_stacks: the job table
     kWsBlocksWideTri,       // figh_tsqr_selected_blocks: level-0 triangles of the wide blocks
-    kWsLinkPos,             // regressor_tsqr_impl: the link map of the link-compact layout
+    kWsLinkPos,             // ChunkW::columns (regressor_tsqr_impl): the link map of the link-compact layout
     kWsBlocksMidTri,        // figh_tsqr_selected_blocks: level-0 triangles of the mid blocks
     kWsFusedBatchTri,       // figh_regressor_tsqr_batch_fused: the consumers' triangles of every workgroup
     kWsDynamicsState,       // figh_regressor_apply (tree kernel): per-wave link wrenches and transforms
@@ -196,6 +196,10 @@ int launch_tsqr_wide(const double *W, long rows, long ldw, const int *col_idx, i
 // in force rows (d_fsel: n columns, then n positions in the kept list) and the force rows' triangle over all kept columns
 int split_force_columns(const int *d_kept, int n, int link_stride, int *d_fsel, int force_compact = 0);
 int embed_force_triangle(const double *d_Rf, int ncf, int nf, const int *d_fpos, int nc, int n, double *d_out);
+// the tail of the split (figh_tsqr_selected_wrench, the streamed TSQR): the force rows' cnt_f level-0 triangles -> d_Rf ->
+// embedded behind the *count triangles of d_stack (nc x nc each, room for one more); ++*count
+int append_force_triangle(const double *d_tri_f, int64_t cnt_f, int ncf, int nf, const int *d_fpos, double *d_Rf, int nc, int n,
+                          double *d_stack, int64_t *count);
 // figh_tsqr_group.hip: the narrow row blocks of a tree's joint-torque regressor as jobs of grouped launches
 struct Tsqr2Job {
     const double *W;       // the block's rows (its own matrix in the block-compact layout)

@@ -517,6 +517,15 @@ static int reduce_to_one(const double *tri, long count, int nc, double *d_R_out)
     return FIGH_OK;
 }
 
+// the tail of the force / torque split (figh_internal.h)
+int append_force_triangle(const double *d_tri_f, int64_t cnt_f, int ncf, int nf, const int *d_fpos, double *d_Rf, int nc, int n,
+                          double *d_stack, int64_t *count) {
+    if (int rc = reduce_to_one(d_tri_f, cnt_f, ncf, d_Rf)) return rc;
+    if (int rc = embed_force_triangle(d_Rf, ncf, nf, d_fpos, nc, n, d_stack + (size_t)*count * nc * nc)) return rc;
+    ++*count;
+    return FIGH_OK;
+}
+
 }  // namespace figh
 
 using namespace figh;
@@ -915,14 +924,13 @@ int figh_tsqr_selected_wrench(const double *d_W, int64_t rows, int64_t ldw, cons
     if (int rc = split_force_columns(d_sel + 2, n, link_stride, fsel, ld_force > 0 ? 1 : 0)) return rc;  // (zero-fills behind the count)
     const int64_t rows_f = rows / 2;
     const int64_t ldf = ld_force > 0 ? ld_force : ldw;  // force-compact: the force rows are a matrix of their own
-    // ---- force rows: their own TSQR over nf columns, reduced to one triangle
+    // ---- force rows: their own level 0 over nf columns (reduced to one triangle behind the torque rows' launch)
     const int64_t cap_f = tsqr_level0_capacity(ncf);
     double *tri_f = static_cast<double *>(workspace(sizeof(double) * (size_t)ncf * ncf * cap_f, kWsForceOrBlockTri));
     double *Rf = static_cast<double *>(workspace(sizeof(double) * (size_t)ncf * ncf, kWsForceOrBlockR));
     if (!tri_f || !Rf) return FIGH_ERR_ALLOC;
     int64_t cnt_f = 0;
     if (int rc = tsqr_level0(d_W, rows_f, ldf, fsel, nf, d_tau, nullptr, 0, tri_f, cap_f, &cnt_f, nullptr)) return rc;
-    if (int rc = reduce_to_one(tri_f, cnt_f, ncf, Rf)) return rc;
     // ---- torque rows: chained launch, workgroup 0 starts from the embedded force triangle, the others from zeros
     long wgs = tsqr_wide_workgroups(nc, cu_count());
     {
@@ -942,10 +950,8 @@ int figh_tsqr_selected_wrench(const double *d_W, int64_t rows, int64_t ldw, cons
     if (int rc = tsqr_level0(d_W + rows_f * ldf, rows - rows_f, ldw, d_sel + 2, n, d_tau ? d_tau + rows_f : nullptr, nullptr,
                              0, stack, wgs + 2, &cnt, nullptr, torque))
         return rc;
-    hipLaunchKernelGGL(embed_force_triangle_kernel, dim3(1), dim3(1024), 0, stream(), Rf, ncf, nf, fsel + n, nc, n,
-                       stack + (size_t)cnt * nc * nc);
-    FIGH_HIP(hipGetLastError());
-    return tsqr_reduce_stack(stack, cnt + 1, nc, n, tol_qr, d_R_out);
+    if (int rc = append_force_triangle(tri_f, cnt_f, ncf, nf, fsel + n, Rf, nc, n, stack, &cnt)) return rc;
+    return tsqr_reduce_stack(stack, cnt, nc, n, tol_qr, d_R_out);
 }
 
 // figh_tsqr_selected for the joint-torque regressor of a TREE of single-dof joints (regressor.py:45-87): row block j (the

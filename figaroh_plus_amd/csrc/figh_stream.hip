@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "figh_internal.h"
+#include "figh_stream_plan.h"
 
 using namespace figh;
 
@@ -38,12 +39,47 @@ __global__ __launch_bounds__(256) void pad_columns_kernel(const int32_t *__restr
     }
 }
 
-int64_t default_chunk(int rps, int ncols) {
-    // ~2 GB of W per chunk: large enough to fill the chip (2048 waves x >= 8 tiles), small next to 288 GB
-    int64_t c = (int64_t)(2.0e9 / (8.0 * rps * ncols));
-    c = (c / 64) * 64;
-    return c < 64 ? 64 : c;
-}
+// The W of a streamed chunk or of a whole batch, in a library workspace of the caller's: its layout (figh_stream_plan.h), the
+// caller's column list in its numbering, and the regressor entry that writes it.
+struct ChunkW {
+    bool padded;
+    int64_t ldc;
+    int flags;                        // the caller's, + FIGH_FLAG_LINK_COMPACT once columns() got a link map
+    const int32_t *d_cols = nullptr;  // columns(): the caller's list in W's numbering
+
+    // nlive > 0: the link-compact layout with that many link segments
+    ChunkW(figh_model_t model, int mode, int flags, int ncols, int nlive = -1)
+        : padded(chunk_w_padded(model->is_chain, mode, flags)), ldc(chunk_w_ld(padded, nlive, model->host.nlinks, ncols)),
+          flags(flags) {}
+
+    // link_pos (host, one entry per link; nullptr: none) goes to the device, and a padded layout gets the translated list
+    int columns(figh_model_t model, const int32_t *d_col_idx, int n, const int *link_pos) {
+        int *d_link_pos = nullptr;
+        if (link_pos) {
+            d_link_pos = static_cast<int *>(workspace(sizeof(int) * kMaxJoints, kWsLinkPos));
+            if (!d_link_pos) return FIGH_ERR_ALLOC;
+            FIGH_HIP(hipMemcpyAsync(d_link_pos, link_pos, sizeof(int) * model->host.nlinks, hipMemcpyHostToDevice, stream()));
+            FIGH_HIP(hipStreamSynchronize(stream()));  // (link_pos is the caller's memory)
+            flags |= FIGH_FLAG_LINK_COMPACT;
+        }
+        d_cols = d_col_idx;
+        if (!padded) return FIGH_OK;
+        int32_t *out = static_cast<int32_t *>(workspace(sizeof(int32_t) * (size_t)n, kWsChunkNormsOrCols));
+        if (!out) return FIGH_ERR_ALLOC;
+        hipLaunchKernelGGL(pad_columns_kernel, dim3((n + 255) / 256), dim3(256), 0, stream(), d_col_idx, n, out,
+                           (const int *)d_link_pos);
+        FIGH_HIP(hipGetLastError());
+        d_cols = out;
+        return FIGH_OK;
+    }
+
+    // W of `ns` samples into Wc (rps * ns rows of ldc); d_colsq (nullable): diag(W^T W) of all columns
+    int build(figh_model_t model, int mode, int ft_mask, int64_t ns, const double *d_q, const double *d_v, const double *d_a,
+              double *Wc, double *d_colsq) const {
+        return padded ? figh_regressor_build_padded(model, mode, flags, ft_mask, ns, d_q, d_v, d_a, Wc, ldc, d_colsq)
+                      : figh_regressor_build(model, mode, flags, ft_mask, ns, d_q, d_v, d_a, Wc, ldc, d_colsq);
+    }
+};
 
 // the caller's column list on the host (a NULL list = all n columns)
 int host_column_list(const int32_t *d_col_idx, int n, std::vector<int32_t> &cols) {
@@ -71,16 +107,14 @@ extern "C" int figh_regressor_colsq(figh_model_t model, int mode, int flags, int
             return rc;
         return FIGH_OK;
     }
-    if (chunk_samples == 0) chunk_samples = default_chunk(rps, ncols);
-    const int64_t cs = chunk_samples < N ? chunk_samples : N;
+    const int64_t cs = chunk_size(N, chunk_samples, rps, ncols);
     double *Wc = static_cast<double *>(workspace(sizeof(double) * (size_t)rps * cs * ncols, kWsChunkW));
     double *part = static_cast<double *>(workspace(sizeof(double) * ncols, kWsChunkNormsOrCols));
     if (!Wc || !part) return FIGH_ERR_ALLOC;
     const int nq = model->host.nq, nv = model->host.nv;
     for (int64_t lo = 0; lo < N; lo += cs) {
-        const int64_t nc_ = (lo + cs <= N) ? cs : N - lo;
-        if (int rc = figh_regressor_build(model, mode, flags, ft_mask, nc_, d_q + lo * nq, d_v + lo * nv, d_a + lo * nv, Wc,
-                                          ncols, part))
+        if (int rc = figh_regressor_build(model, mode, flags, ft_mask, chunk_samples_at(lo, cs, N), d_q + lo * nq,
+                                          d_v + lo * nv, d_a + lo * nv, Wc, ncols, part))
             return rc;
         hipLaunchKernelGGL(vec_add_kernel, dim3((ncols + 255) / 256), dim3(256), 0, stream(), d_colsq, part, ncols);
         FIGH_HIP(hipGetLastError());
@@ -88,17 +122,170 @@ extern "C" int figh_regressor_colsq(figh_model_t model, int mode, int flags, int
     return FIGH_OK;
 }
 
-static int regressor_tsqr_impl(figh_model_t model, int mode, int flags, int ft_mask, int64_t N, const double *d_q,
-                               const double *d_v, const double *d_a, const int32_t *d_col_idx, int n, const double *d_tau,
-                               const double *h_block_weight, int nblocks, int64_t chunk_samples, double *d_R_out,
-                               double *d_colsq_out);
+// ---- The streamed TSQR (figh_regressor_tsqr, _tsqr_norms and, through the first, _gram) in phases: the argument checks,
+// one fetch of the column list, the plan (figh_stream_plan.h: every decision, nothing launched), workspaces sized from it,
+// the chunk loop that only executes it, the merge.
+namespace {
+
+struct StreamArgs {  // figh_regressor_tsqr_norms' arguments (d_colsq_out nullable)
+    figh_model_t model;
+    int mode, flags, ft_mask;
+    int64_t N;
+    const double *d_q, *d_v, *d_a;
+    const int32_t *d_col_idx;
+    int n;
+    const double *d_tau, *h_block_weight;
+    int nblocks;
+    int64_t chunk_samples;
+    double *d_R_out, *d_colsq_out;
+};
+
+// phase 1: refuse, or zero what the chunks accumulate into; *done: no samples, the outputs are final
+int check_stream_args(const StreamArgs &a, int *rps, int *ncols, bool *done) {
+    if (int rc = figh_regressor_shape(a.model, a.mode, a.flags, rps, ncols)) return rc;
+    FIGH_REQUIRE(a.N >= 0 && a.chunk_samples >= 0, "negative size");
+    FIGH_REQUIRE(a.d_q && a.d_v && a.d_a && a.d_R_out, "NULL device pointer");
+    FIGH_REQUIRE(a.n >= 1 && (a.d_col_idx ? a.n <= *ncols : a.n == *ncols), "bad column count");
+    if (a.h_block_weight)
+        FIGH_REQUIRE(a.nblocks > 0 && *rps % a.nblocks == 0, "row-block weights must divide the rows of a sample");
+    if (int rc = ensure_device()) return rc;
+    if (a.d_colsq_out) FIGH_HIP(hipMemsetAsync(a.d_colsq_out, 0, sizeof(double) * *ncols, stream()));
+    *done = a.N == 0;
+    if (*done) {
+        const int nc = a.n + (a.d_tau ? 1 : 0);
+        FIGH_HIP(hipMemsetAsync(a.d_R_out, 0, sizeof(double) * (size_t)nc * nc, stream()));
+        return FIGH_OK;
+    }
+    const int64_t cs = chunk_size(a.N, a.chunk_samples, *rps, *ncols);
+    FIGH_REQUIRE(!(a.flags & FIGH_FLAG_BLOCKED_INPUTS) || cs >= a.N || cs % 64 == 0,
+                 "tile-blocked inputs: chunk_samples must be a multiple of 64");
+    return FIGH_OK;
+}
+
+// phase 3: the call as stream_plan sees it (cols: the caller's list on the host; link_pos: kMaxJoints entries, filled here)
+StreamPlan plan_stream(const StreamArgs &a, int rps, int ncols, const std::vector<int32_t> &cols, int *link_pos) {
+    const DevModel &h = a.model->host;
+    StreamCall c;
+    c.rps = rps, c.ncols = ncols;
+    c.nlinks = h.nlinks, c.nv = h.nv, c.njoints = h.njoints;
+    c.is_chain = a.model->is_chain;
+    c.free_flyer = h.njoints > 1 && h.jtype[1] == FIGH_JT_FREEFLYER;
+    c.mode = a.mode, c.flags = a.flags;
+    c.with_tau = a.d_tau != nullptr, c.weighted = a.h_block_weight != nullptr;
+    c.N = a.N, c.chunk_samples = a.chunk_samples;
+    c.cols = cols.data(), c.n = a.n;
+    c.link_pos = link_pos;
+    c.nlive = tree_link_positions(a.model, a.mode, a.flags & 7, a.ft_mask, link_pos);
+    c.chain_capacity = tsqr_level0_capacity(a.n + (a.d_tau ? 1 : 0)) - 1;
+    return stream_plan(c);
+}
+
+// phase 4: the workspaces, sized from the plan
+struct StreamWork {
+    int64_t per_chunk = 0, cap_f = 0;  // level-0 triangles one launch can produce: all rows / torque rows, force rows
+    double *Wc = nullptr, *tc = nullptr, *cs_part = nullptr, *stack = nullptr;
+    int *fsel = nullptr;
+    double *stack_f = nullptr, *Rf = nullptr;
+
+    int allocate(const StreamArgs &a, const StreamPlan &p) {
+        const int nc = p.nc, ncf = p.ncf;
+        // diag(W^T W) of all columns fused into the regressor kernel of every chunk (the elimination's input, for a caller
+        // that factors the columns it EXPECTS to be kept and verifies the set afterwards: no separate norms pass over the
+        // samples)
+        if (a.d_colsq_out) cs_part = static_cast<double *>(workspace(sizeof(double) * p.ncols, kWsChunkNormsFused));
+        Wc = static_cast<double *>(workspace(sizeof(double) * (size_t)p.rps * p.cs * p.ldc, kWsChunkW));
+        if (a.d_tau) tc = static_cast<double *>(workspace(sizeof(double) * (size_t)p.rps * p.cs, kWsChunkTau));
+        // level-0 triangles of ALL chunks are stacked and the merge tree runs once (a merge is latency-bound: running it
+        // per chunk cost 158 ms of the 1.24 s human pass)
+        per_chunk = tsqr_level0_capacity(nc);
+        stack = static_cast<double *>(workspace(sizeof(double) * (size_t)p.nchunks * per_chunk * nc * nc, kWsChunkStack));
+        if ((a.d_colsq_out && !cs_part) || !Wc || (a.d_tau && !tc) || !stack) return FIGH_ERR_ALLOC;
+        if (!p.split) return FIGH_OK;
+        cap_f = tsqr_level0_capacity(ncf);
+        fsel = static_cast<int *>(workspace(sizeof(int) * 2 * (size_t)p.n, kWsForceCols));
+        // the force rows' level-0 triangles of ALL chunks are stacked and merged once (a merge per chunk cost 0.175 ms x 20
+        // for the human model)
+        stack_f = static_cast<double *>(workspace(sizeof(double) * (size_t)ncf * ncf * cap_f * p.nchunks, kWsChunkForceStack));
+        Rf = static_cast<double *>(workspace(sizeof(double) * (size_t)ncf * ncf, kWsForceOrBlockR));
+        return fsel && stack_f && Rf ? FIGH_OK : FIGH_ERR_ALLOC;
+    }
+};
+
+// phase 5: the chunk of the samples from `lo` on -- W, the norms, tau, the level-0 launches the plan says; *have, *have_f:
+// the triangles in w.stack and w.stack_f
+int run_chunk(const StreamArgs &a, const StreamPlan &p, const ChunkW &cw, const StreamWork &w, int64_t lo, int64_t *have,
+              int64_t *have_f) {
+    const int rps = p.rps, n = p.n, nc = p.nc, nq = a.model->host.nq, nv = a.model->host.nv;
+    const int64_t nc_ = chunk_samples_at(lo, p.cs, a.N), ldc = p.ldc;
+    if (int rc = cw.build(a.model, a.mode, a.ft_mask, nc_, a.d_q + lo * nq, a.d_v + lo * nv, a.d_a + lo * nv, w.Wc, w.cs_part))
+        return rc;
+    if (w.cs_part) {
+        hipLaunchKernelGGL(vec_add_kernel, dim3((p.ncols + 255) / 256), dim3(256), 0, stream(), a.d_colsq_out, w.cs_part,
+                           p.ncols);
+        FIGH_HIP(hipGetLastError());
+    }
+    if (a.d_tau)  // rows j*N + [lo, lo + nc_) of tau -> the chunk's joint-major vector (rows j*nc_ + i)
+        FIGH_HIP(hipMemcpy2DAsync(w.tc, sizeof(double) * nc_, a.d_tau + lo, sizeof(double) * a.N, sizeof(double) * nc_, rps,
+                                  hipMemcpyDeviceToDevice, stream()));
+    Level0Options torque;  // (the torque rows: all of the chunk's rows unless it is split)
+    if (p.hinted(nc_)) {
+        if (int rc = tile_hint(p.first.data(), rps, (int64_t)rps * nc_, n, nc, &torque.hint)) return rc;
+    }
+    const int64_t rows_f = p.split ? 3 * nc_ : 0;  // the chunk's force rows (row blocks 0 .. 2 of its joint-major W)
+    if (p.split) {
+        int64_t cnt_f = 0;
+        if (int rc = tsqr_level0(w.Wc, rows_f, ldc, w.fsel, p.nf, w.tc, nullptr, 0, w.stack_f + (size_t)*have_f * p.ncf * p.ncf,
+                                 w.cap_f, &cnt_f, nullptr))
+            return rc;
+        *have_f += cnt_f;
+    }
+    if (p.chained) {
+        torque.chain_wgs = p.chain_wgs;
+        torque.chain_flags = lo > 0 ? 1 : 0;
+    }
+    int64_t got = 0;
+    if (int rc = tsqr_level0(w.Wc + rows_f * ldc, (int64_t)rps * nc_ - rows_f, ldc, cw.d_cols, n, w.tc ? w.tc + rows_f : nullptr,
+                             a.h_block_weight, a.nblocks, w.stack + (size_t)(p.chained ? 0 : *have) * nc * nc, w.per_chunk,
+                             &got, nullptr, torque))
+        return rc;
+    *have = p.chained ? got : *have + got;
+    return FIGH_OK;
+}
+
+int regressor_tsqr_impl(const StreamArgs &a) {
+    int rps = 0, ncols = 0;
+    bool done = false;
+    if (int rc = check_stream_args(a, &rps, &ncols, &done)) return rc;
+    if (done) return FIGH_OK;
+    std::vector<int32_t> cols;
+    if (int rc = host_column_list(a.d_col_idx, a.n, cols)) return rc;
+    int link_pos[kMaxJoints];
+    const StreamPlan p = plan_stream(a, rps, ncols, cols, link_pos);
+    ChunkW cw(a.model, a.mode, a.flags, ncols, p.nlive);
+    if (int rc = cw.columns(a.model, a.d_col_idx, a.n, p.compact ? link_pos : nullptr)) return rc;
+    StreamWork w;
+    if (int rc = w.allocate(a, p)) return rc;
+    if (p.split)
+        if (int rc = split_force_columns(cw.d_cols, p.n, cw.padded ? 16 : 14, w.fsel)) return rc;
+    int64_t have = 0, have_f = 0;
+    for (int64_t lo = 0; lo < a.N; lo += p.cs)
+        if (int rc = run_chunk(a, p, cw, w, lo, &have, &have_f)) return rc;
+    FIGH_REQUIRE(have < (1LL << 31), "too many level-0 triangles");
+    if (p.split) {  // the force rows' triangle of all chunks, over all kept columns, as one more element of the stack
+        FIGH_REQUIRE(have_f < (1LL << 31), "too many level-0 triangles");
+        if (int rc = append_force_triangle(w.stack_f, have_f, p.ncf, p.nf, w.fsel + p.n, w.Rf, p.nc, p.n, w.stack, &have)) return rc;
+    }
+    return figh_tsqr_merge(w.stack, (int)have, p.nc, a.d_R_out);
+}
+
+}  // namespace
 
 extern "C" int figh_regressor_tsqr(figh_model_t model, int mode, int flags, int ft_mask, int64_t N, const double *d_q,
                                    const double *d_v, const double *d_a, const int32_t *d_col_idx, int n,
                                    const double *d_tau, const double *h_block_weight, int nblocks, int64_t chunk_samples,
                                    double *d_R_out) {
-    return regressor_tsqr_impl(model, mode, flags, ft_mask, N, d_q, d_v, d_a, d_col_idx, n, d_tau, h_block_weight, nblocks,
-                               chunk_samples, d_R_out, nullptr);
+    return regressor_tsqr_impl({model, mode, flags, ft_mask, N, d_q, d_v, d_a, d_col_idx, n, d_tau, h_block_weight, nblocks,
+                                chunk_samples, d_R_out, nullptr});
 }
 
 extern "C" int figh_regressor_tsqr_norms(figh_model_t model, int mode, int flags, int ft_mask, int64_t N, const double *d_q,
@@ -106,175 +293,8 @@ extern "C" int figh_regressor_tsqr_norms(figh_model_t model, int mode, int flags
                                          const double *d_tau, const double *h_block_weight, int nblocks,
                                          int64_t chunk_samples, double *d_R_out, double *d_colsq_out) {
     FIGH_REQUIRE(d_colsq_out, "NULL device pointer");
-    return regressor_tsqr_impl(model, mode, flags, ft_mask, N, d_q, d_v, d_a, d_col_idx, n, d_tau, h_block_weight, nblocks,
-                               chunk_samples, d_R_out, d_colsq_out);
-}
-
-static int regressor_tsqr_impl(figh_model_t model, int mode, int flags, int ft_mask, int64_t N, const double *d_q,
-                               const double *d_v, const double *d_a, const int32_t *d_col_idx, int n, const double *d_tau,
-                               const double *h_block_weight, int nblocks, int64_t chunk_samples, double *d_R_out,
-                               double *d_colsq_out) {
-    int rps = 0, ncols = 0;
-    if (int rc = figh_regressor_shape(model, mode, flags, &rps, &ncols)) return rc;
-    FIGH_REQUIRE(N >= 0 && chunk_samples >= 0, "negative size");
-    FIGH_REQUIRE(d_q && d_v && d_a && d_R_out, "NULL device pointer");
-    FIGH_REQUIRE(n >= 1 && (d_col_idx ? n <= ncols : n == ncols), "bad column count");
-    if (h_block_weight) FIGH_REQUIRE(nblocks > 0 && rps % nblocks == 0, "row-block weights must divide the rows of a sample");
-    if (int rc = ensure_device()) return rc;
-    const int nc = n + (d_tau ? 1 : 0);
-    if (d_colsq_out) FIGH_HIP(hipMemsetAsync(d_colsq_out, 0, sizeof(double) * ncols, stream()));
-    if (N == 0) {
-        FIGH_HIP(hipMemsetAsync(d_R_out, 0, sizeof(double) * (size_t)nc * nc, stream()));
-        return FIGH_OK;
-    }
-    if (chunk_samples == 0) chunk_samples = default_chunk(rps, ncols);
-    const int64_t cs = chunk_samples < N ? chunk_samples : N;
-    const int64_t nchunks = (N + cs - 1) / cs;
-    // diag(W^T W) of all columns fused into the regressor kernel of every chunk (the elimination's input, for a caller that
-    // factors the columns it EXPECTS to be kept and verifies the set afterwards: no separate norms pass over the samples)
-    double *cs_part = d_colsq_out ? static_cast<double *>(workspace(sizeof(double) * ncols, kWsChunkNormsFused)) : nullptr;
-    if (d_colsq_out && !cs_part) return FIGH_ERR_ALLOC;
-    FIGH_REQUIRE(!(flags & FIGH_FLAG_BLOCKED_INPUTS) || nchunks == 1 || cs % 64 == 0,
-                 "tile-blocked inputs: chunk_samples must be a multiple of 64");
-    // the chunk's W is a private workspace: tree models get the link-padded layout (16 columns per link, every row
-    // segment one 128-byte line) and the caller's column list is translated to it
-    const bool padded = !(model->is_chain && mode == FIGH_MODE_JOINT_TORQUE) && !(flags & FIGH_FLAG_TX40);
-    // external wrench on a free-flyer root: links without entries (massless bodies) get no columns in the chunk's W
-    // (FIGH_FLAG_LINK_COMPACT; the caller's column list can only name them if it keeps columns that are identically zero)
-    int link_pos[kMaxJoints];
-    int *d_link_pos = nullptr;
-    int nlive = padded ? tree_link_positions(model, mode, flags & 7, ft_mask, link_pos) : -1;
-    if (nlive <= 0 || nlive >= model->host.nlinks) nlive = -1;
-    if (nlive > 0) {
-        // a caller may list columns of links without entries (identically zero columns: the SIP program passes the inertial
-        // columns of EVERY link, identification_tools.py:528-531): those exist in the link-padded layout only
-        std::vector<int32_t> cols;
-        if (int rc = host_column_list(d_col_idx, n, cols)) return rc;
-        for (int c = 0; c < n && nlive > 0; ++c)
-            if (cols[c] < 0 || cols[c] / 14 >= model->host.nlinks || link_pos[cols[c] / 14] < 0) nlive = -1;
-    }
-    if (nlive > 0) {
-        d_link_pos = static_cast<int *>(workspace(sizeof(int) * kMaxJoints, kWsLinkPos));
-        if (!d_link_pos) return FIGH_ERR_ALLOC;
-        FIGH_HIP(hipMemcpyAsync(d_link_pos, link_pos, sizeof(int) * model->host.nlinks, hipMemcpyHostToDevice, stream()));
-        FIGH_HIP(hipStreamSynchronize(stream()));  // (link_pos lives on this stack frame)
-        flags |= FIGH_FLAG_LINK_COMPACT;
-    }
-    const int64_t ldc = padded ? 16 * (int64_t)(nlive > 0 ? nlive : model->host.nlinks) : ncols;
-    double *Wc = static_cast<double *>(workspace(sizeof(double) * (size_t)rps * cs * ldc, kWsChunkW));
-    int32_t *d_cols = const_cast<int32_t *>(d_col_idx);
-    if (padded) {
-        d_cols = static_cast<int32_t *>(workspace(sizeof(int32_t) * (size_t)n, kWsChunkNormsOrCols));
-        if (!d_cols) return FIGH_ERR_ALLOC;
-        hipLaunchKernelGGL(pad_columns_kernel, dim3((n + 255) / 256), dim3(256), 0, stream(), d_col_idx, n, d_cols,
-                           (const int *)d_link_pos);
-        FIGH_HIP(hipGetLastError());
-    }
-    double *tc = d_tau ? static_cast<double *>(workspace(sizeof(double) * (size_t)rps * cs, kWsChunkTau)) : nullptr;
-    // level-0 triangles of ALL chunks are stacked and the merge tree runs once (a merge is latency-bound: running it
-    // per chunk cost 158 ms of the 1.24 s human pass)
-    const int64_t per_chunk = tsqr_level0_capacity(nc);
-    double *stack = static_cast<double *>(workspace(sizeof(double) * (size_t)nchunks * per_chunk * nc * nc, kWsChunkStack));
-    if (!Wc || (d_tau && !tc) || !stack) return FIGH_ERR_ALLOC;
-    const int nq = model->host.nq, nv = model->host.nv;
-    // joint-torque regressor of single-dof joints: the rows of joint j only involve the links from j on, so the kept
-    // columns in front of 14 j are exact zeros in row block j -- the structure hint of figh_tsqr_structured
-    std::vector<int32_t> first;
-    if (mode == FIGH_MODE_JOINT_TORQUE && nv == model->host.njoints - 1 && nc <= 80 && cs >= 64) {
-        std::vector<int32_t> cols;
-        if (int rc = host_column_list(d_col_idx, n, cols)) return rc;
-        bool sorted = true;
-        for (int c = 1; c < n; ++c) sorted = sorted && cols[c - 1] < cols[c];
-        if (sorted) {
-            first.resize(rps);
-            for (int j = 0; j < rps; ++j) {
-                int f = 0;
-                while (f < n && cols[f] < 14 * j) ++f;
-                first[j] = f;
-            }
-        }
-    }
-    // More than 80 columns and several chunks: CHAINED launches -- every workgroup of the blocked kernel keeps ONE running
-    // triangle across the chunks (same workgroup count in every launch; a launch starts from the triangle the previous one
-    // wrote), so the stack to merge holds one launch's triangles instead of nchunks times as many (human model, 20 chunks:
-    // 512 instead of 10 240 triangles, merges 8.3 -> 1.8 ms).
-    const bool chained = nc > 80 && nchunks > 1;
-    // External wrench on a free-flyer root: per chunk the three force row blocks are factored over the nf columns that can
-    // be non-zero there (rotational-inertia columns are exact zeros in force rows, figh_tsqr_selected_wrench) and reduced to
-    // one triangle per chunk; the torque row blocks go through the (chained) launches over all columns.
-    int nf = 0;
-    if (mode == FIGH_MODE_EXT_WRENCH && rps == 6 && model->host.njoints > 1 && model->host.jtype[1] == FIGH_JT_FREEFLYER &&
-        !(flags & FIGH_FLAG_TX40) && !h_block_weight && nc > 80 && 3 * cs >= 16L * nc) {
-        std::vector<int32_t> cols;
-        if (int rc = host_column_list(d_col_idx, n, cols)) return rc;
-        for (int c = 0; c < n; ++c) nf += (cols[c] % 14) >= 6;
-        if (nf >= n) nf = 0;
-    }
-    const bool split = nf > 0;
-    const int ncf = nf + (d_tau ? 1 : 0);
-    const long rsplit = split ? 2 : 1;  // the torque rows are half of a chunk
-    int *fsel = nullptr;
-    double *tri_f = nullptr, *stack_f = nullptr, *Rf = nullptr;
-    int64_t cap_f = 0;
-    if (split) {
-        cap_f = tsqr_level0_capacity(ncf);
-        fsel = static_cast<int *>(workspace(sizeof(int) * 2 * (size_t)n, kWsForceCols));
-        // the force rows' level-0 triangles of ALL chunks are stacked and merged once (a merge per chunk cost 0.175 ms x 20
-        // for the human model)
-        stack_f = static_cast<double *>(workspace(sizeof(double) * (size_t)ncf * ncf * cap_f * nchunks, kWsChunkForceStack));
-        tri_f = stack_f;
-        Rf = static_cast<double *>(workspace(sizeof(double) * (size_t)ncf * ncf, kWsForceOrBlockR));
-        if (!fsel || !tri_f || !stack_f || !Rf) return FIGH_ERR_ALLOC;
-        if (int rc = split_force_columns(d_cols, n, padded ? 16 : 14, fsel)) return rc;
-    }
-    const long chain_wgs =
-        chained ? std::min<long>(per_chunk - 1, std::max<long>(1, (long)rps * cs / rsplit / (8L * nc))) : 0;
-    int64_t have = 0, have_f = 0;
-    for (int64_t lo = 0; lo < N; lo += cs) {
-        const int64_t nc_ = (lo + cs <= N) ? cs : N - lo;
-        if (int rc = padded ? figh_regressor_build_padded(model, mode, flags, ft_mask, nc_, d_q + lo * nq, d_v + lo * nv,
-                                                          d_a + lo * nv, Wc, ldc, cs_part)
-                            : figh_regressor_build(model, mode, flags, ft_mask, nc_, d_q + lo * nq, d_v + lo * nv,
-                                                   d_a + lo * nv, Wc, ldc, cs_part))
-            return rc;
-        if (cs_part) {
-            hipLaunchKernelGGL(vec_add_kernel, dim3((ncols + 255) / 256), dim3(256), 0, stream(), d_colsq_out, cs_part, ncols);
-            FIGH_HIP(hipGetLastError());
-        }
-        if (d_tau)  // rows j*N + [lo, lo + nc_) of tau -> the chunk's joint-major vector (rows j*nc_ + i)
-            FIGH_HIP(hipMemcpy2DAsync(tc, sizeof(double) * nc_, d_tau + lo, sizeof(double) * N, sizeof(double) * nc_, rps,
-                                      hipMemcpyDeviceToDevice, stream()));
-        Level0Options torque;  // (the torque rows: all of the chunk's rows unless it is split)
-        if (!first.empty() && nc_ >= 64) {
-            if (int rc = tile_hint(first.data(), rps, (int64_t)rps * nc_, n, nc, &torque.hint)) return rc;
-        }
-        const int64_t rows_f = split ? 3 * nc_ : 0;  // the chunk's force rows (row blocks 0 .. 2 of its joint-major W)
-        if (split) {
-            int64_t cnt_f = 0;
-            if (int rc = tsqr_level0(Wc, rows_f, ldc, fsel, nf, tc, nullptr, 0, stack_f + (size_t)have_f * ncf * ncf, cap_f,
-                                     &cnt_f, nullptr))
-                return rc;
-            have_f += cnt_f;
-        }
-        if (chained) {
-            torque.chain_wgs = chain_wgs;
-            torque.chain_flags = lo > 0 ? 1 : 0;
-        }
-        int64_t got = 0;
-        if (int rc = tsqr_level0(Wc + rows_f * ldc, (int64_t)rps * nc_ - rows_f, ldc, d_cols, n, tc ? tc + rows_f : nullptr,
-                                 h_block_weight, nblocks, stack + (size_t)(chained ? 0 : have) * nc * nc, per_chunk, &got,
-                                 nullptr, torque))
-            return rc;
-        have = chained ? got : have + got;
-    }
-    FIGH_REQUIRE(have < (1LL << 31), "too many level-0 triangles");
-    if (split) {  // the force rows' triangle of all chunks, over all kept columns, as one more element of the stack
-        FIGH_REQUIRE(have_f < (1LL << 31), "too many level-0 triangles");
-        if (int rc = figh_tsqr_merge(stack_f, (int)have_f, ncf, Rf)) return rc;
-        if (int rc = embed_force_triangle(Rf, ncf, nf, fsel + n, nc, n, stack + (size_t)have * nc * nc)) return rc;
-        ++have;
-    }
-    return figh_tsqr_merge(stack, (int)have, nc, d_R_out);
+    return regressor_tsqr_impl({model, mode, flags, ft_mask, N, d_q, d_v, d_a, d_col_idx, n, d_tau, h_block_weight, nblocks,
+                                chunk_samples, d_R_out, d_colsq_out});
 }
 
 // triangles of the previous trajectories (common) and of trajectory b, interleaved: the stack of the pair level that
@@ -322,22 +342,13 @@ extern "C" int figh_regressor_tsqr_batch(figh_model_t model, int mode, int flags
     // ---- blocked kernel: ONE K1 launch over all B * n_per samples (the standard joint-major regressor: trajectory b is the
     // rps row segments [j N_tot + b n_per, + n_per)), ONE batched level-0 launch (wgs workgroups per trajectory), then
     // pair levels over the whole stack -- wgs is a power of two, so a pair never straddles two trajectories
-    const bool padded = !(model->is_chain && mode == FIGH_MODE_JOINT_TORQUE) && !(flags & FIGH_FLAG_TX40);
-    const int64_t ldc = padded ? 16 * (int64_t)model->host.nlinks : ncols;
+    ChunkW cw(model, mode, flags, ncols);
+    const int64_t ldc = cw.ldc;
     FIGH_REQUIRE(ldc < (1L << 21), "figh_tsqr: more than 80 columns need a leading dimension below 2^21 elements");
     double *Wc = static_cast<double *>(workspace(sizeof(double) * (size_t)rps * N_tot * ldc, kWsChunkW));
     if (!Wc) return FIGH_ERR_ALLOC;
-    int32_t *d_cols = const_cast<int32_t *>(d_col_idx);
-    if (padded) {
-        d_cols = static_cast<int32_t *>(workspace(sizeof(int32_t) * (size_t)n, kWsChunkNormsOrCols));
-        if (!d_cols) return FIGH_ERR_ALLOC;
-        hipLaunchKernelGGL(pad_columns_kernel, dim3((n + 255) / 256), dim3(256), 0, stream(), d_col_idx, n, d_cols,
-                           (const int *)nullptr);
-        FIGH_HIP(hipGetLastError());
-    }
-    if (int rc = padded ? figh_regressor_build_padded(model, mode, flags, ft_mask, N_tot, d_q, d_v, d_a, Wc, ldc, nullptr)
-                        : figh_regressor_build(model, mode, flags, ft_mask, N_tot, d_q, d_v, d_a, Wc, ldc, nullptr))
-        return rc;
+    if (int rc = cw.columns(model, d_col_idx, n, nullptr)) return rc;
+    if (int rc = cw.build(model, mode, ft_mask, N_tot, d_q, d_v, d_a, Wc, nullptr)) return rc;
     const long M = tsqr_wide_tile_rows(nc);
     const long tiles = rps * ((n_per + M - 1) / M);
     // workgroups per trajectory: enough in total to fill the chip twice over, a leaf at least four tiles and 4 nc rows tall
@@ -348,7 +359,7 @@ extern "C" int figh_regressor_tsqr_batch(figh_model_t model, int mode, int flags
     if (!stack) return FIGH_ERR_ALLOC;
     {
         ProfileScope scope("tsqr_batch");
-        if (int rc = launch_tsqr_wide_batch(Wc, ldc, d_cols, n, nc, B, n_per, rps, N_tot, wgs, stack)) return rc;
+        if (int rc = launch_tsqr_wide_batch(Wc, ldc, cw.d_cols, n, nc, B, n_per, rps, N_tot, wgs, stack)) return rc;
     }
     const double *cur = stack;
     WorkspaceSlot slot = kWsMergeA;

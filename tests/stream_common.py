@@ -1,12 +1,16 @@
 """Host side of the streamed-TSQR tests (tests/test_streamed_plan_host.py, tests/test_streamed_columnwise.py).
 
-``stream_plan`` mirrors, from the source, every decision ``regressor_tsqr_impl`` (csrc/figh_stream.hip) takes on the host
-before and inside its chunk loop; ``CASES`` is the table of calls the GPU tests make, and the host test asserts through the
-mirror that the table reaches every branch of that loop.  Nothing here needs a device.
+``stream_plan`` mirrors every decision ``regressor_tsqr_impl`` (csrc/figh_stream.hip) executes: the library takes them all
+in one pure function, ``figh::stream_plan`` (csrc/figh_stream_plan.h), before it allocates or launches anything.  The mirror
+is written independently in Python and is not trusted from reading: the host test compiles that header into a stand-alone
+program (tools/stream_plan_host.cpp) and asserts that both give the same plan, field by field, for every call of the table
+and of the hand-computed records.  ``CASES`` is the table of calls the GPU tests make, and the host test asserts through
+the mirror that the table reaches every branch of the chunk loop.  Nothing here needs a device.
 
 The mirror leaves out the one device-dependent term: ``chain_wgs`` is also capped at ``tsqr_level0_capacity(nc) - 1``
-(compute units x occupancy of the blocked kernel).  Every case keeps ``rps cs / rsplit / (8 nc)`` at a few workgroups, far
-below any compute-unit count, so the cap never binds (asserted in the host test: at most MAX_CHAIN_WGS).
+(compute units x occupancy of the blocked kernel), an input of the native plan.  Every case keeps
+``rps cs / rsplit / (8 nc)`` at a few workgroups, far below any compute-unit count, so the cap never binds (asserted in the
+host test: at most MAX_CHAIN_WGS); the host test gives the native plan two calls of its own where it does.
 """
 import functools
 from collections import namedtuple
@@ -260,9 +264,14 @@ FULL_RANK = {"a_base_ragged", "d_human_base"}  # cases whose long-double Cholesk
 DEAD_COLUMNS = {"e_fallback": list(range(14, 20))}  # listed columns that are exact zeros (reference numbering)
 
 
-def case_plan(case):
+def case_call(case):
+    """The arguments of stream_plan for a case."""
     param, coupling = case_param(case)
     f = facts(case.model, param, coupling)
     mode, flags, ft = call_flags(param, coupling, case.flags)
-    return stream_plan(f.rps, f.ncols, f.nlinks, f.is_chain, mode, flags, f.free_flyer, f.single_dof, column_list(case),
-                       case.with_tau, case.weights is not None, case.N, case.chunk, live_links(f, mode, flags, ft))
+    return (f.rps, f.ncols, f.nlinks, f.is_chain, mode, flags, f.free_flyer, f.single_dof, column_list(case),
+            case.with_tau, case.weights is not None, case.N, case.chunk, live_links(f, mode, flags, ft))
+
+
+def case_plan(case):
+    return stream_plan(*case_call(case))
