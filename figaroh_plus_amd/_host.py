@@ -86,6 +86,128 @@ def singular_values_batch(R):
     return out
 
 
+def jacobi_round_robin(r):
+    """The sweep of csrc/figh_singular.hip: a list of steps, each ``(p, q)`` index arrays of disjoint column pairs, p < q.
+    With n = r rounded up to even and m = n - 1, step s < m holds the pairs k < n / 2: k = 0: (s, n - 1); k >= 1:
+    ((s + k) mod m, (s - k) mod m); for odd r the pair that holds index r is the bye."""
+    import numpy as np
+    n = r + (r & 1)
+    m = n - 1
+    k = np.arange(n // 2)
+    steps = []
+    for s in range(m):
+        a = np.where(k == 0, s, (s + k) % m)
+        b = np.where(k == 0, n - 1, (s - k) % m)
+        p, q = np.minimum(a, b), np.maximum(a, b)
+        steps.append((p[q < r], q[q < r]))
+    return steps
+
+
+def _jacobi_group_sum(prod):
+    """Sum of the products ``prod`` over the last axis (a multiple of 16 rows) as a 16-lane group of the kernel forms it:
+    lane l adds the products of rows l, l + 16, ... in ascending order, then the lanes meet pairwise (2, 4, 8, 16)."""
+    prod = prod.reshape(prod.shape[:-1] + (-1, 16))
+    acc = prod[..., 0, :]
+    for j in range(1, prod.shape[-2]):
+        acc = acc + prod[..., j, :]
+    while acc.shape[-1] > 1:
+        acc = acc[..., 0::2] + acc[..., 1::2]
+    return acc[..., 0]
+
+
+def jacobi_singular_values_mirror(R, max_sweeps=40, dtype=None):
+    """NumPy mirror of ``figh_singular_values_batch`` (csrc/figh_singular.hip): one-sided Jacobi on the columns of the
+    upper triangle of R (r x r or B x r x r; the strict lower triangle is never read), the same statements in the same
+    order -- the round-robin steps of :func:`jacobi_round_robin`, vectorised over the disjoint pairs of a step and over B.
+    Returns ``(sigma, sweeps, converged)``: sigma (B x r) in column order, unsorted, as the kernel leaves it.  ``dtype``:
+    the arithmetic (default float64; ``np.longdouble`` is the reference of the tests)."""
+    import numpy as np
+    dtype = np.float64 if dtype is None else dtype
+    R = np.asarray(R)
+    A = R.reshape((-1,) + R.shape[-2:])
+    B, r = A.shape[0], A.shape[-1]
+    if A.shape[1] != r or r < 1:
+        raise ValueError("expected r x r matrices, got %r" % (R.shape,))
+    rows = 16 * ((r + 15) // 16)
+    iu = np.triu_indices(r)
+    At = np.zeros((B, r, rows), dtype=dtype)  # At[b, c]: column c
+    At[:, iu[1], iu[0]] = A[:, iu[0], iu[1]]
+    steps = jacobi_round_robin(r)
+    thr, one, two = dtype(2.0) ** -52, dtype(1.0), dtype(2.0)
+    sweeps = np.full(B, max_sweeps, dtype=np.int32)
+    converged = np.zeros(B, dtype=np.int32)
+    live = np.arange(B)  # the matrices still sweeping
+    with np.errstate(all="ignore"):
+        for w in range(max_sweeps):
+            X = At[live]
+            rotated = np.zeros(len(live), dtype=bool)
+            for p, q in steps:
+                if not len(p):
+                    continue
+                n = len(p)
+                both = np.take(X, np.concatenate((p, q)), axis=1)
+                ap, aq = both[:, :n], both[:, n:]
+                prod = np.empty((len(X), 3 * n, rows), dtype=dtype)
+                np.multiply(both, both, out=prod[:, :2 * n])
+                np.multiply(ap, aq, out=prod[:, 2 * n:])
+                sums = _jacobi_group_sum(prod)
+                alpha, beta, gamma = sums[:, :n], sums[:, n:2 * n], sums[:, 2 * n:]
+                rot = ~(np.abs(gamma) <= thr * np.sqrt(alpha * beta))  # (a NaN rotates)
+                if not rot.any():
+                    continue
+                bi, ki = np.nonzero(rot)  # the pairs that rotate
+                ap, aq = ap[bi, ki], aq[bi, ki]
+                zeta = (beta[bi, ki] - alpha[bi, ki]) / (two * gamma[bi, ki])
+                t = np.where(zeta < 0, -one, one) / (np.abs(zeta) + np.sqrt(one + zeta * zeta))
+                c = one / np.sqrt(one + t * t)
+                s = c * t
+                c, s = c[:, None], s[:, None]
+                X[bi, p[ki], :] = c * ap - s * aq
+                X[bi, q[ki], :] = s * ap + c * aq
+                rotated |= rot.any(axis=1)
+            At[live] = X
+            done = live[~rotated]
+            sweeps[done], converged[done] = w + 1, 1
+            live = live[rotated]
+            if not len(live):
+                break
+        sigma = np.sqrt(_jacobi_group_sum(At * At))
+    return sigma, sweeps, converged
+
+
+SINGULAR_VALUES_MAX_SWEEPS = 40  # the float64 mirror needs at most 22 on the graded matrices of the tests
+device_singular_value_fallbacks = 0  # matrices that singular_values_batch_device recomputed on the host (not converged)
+
+
+def singular_values_batch_device(d_R, B, r, max_sweeps=SINGULAR_VALUES_MAX_SWEEPS, return_status=False):
+    """Singular values of the B r x r upper triangles RESIDENT in ``d_R`` (back to back, as figh_regressor_tsqr_batch[_fused]
+    leave them) -> B x r, descending: ``figh_singular_values_batch``; B r doubles and the status come down, not the B r^2 of
+    the triangles.  A matrix the kernel did not bring to convergence within ``max_sweeps`` (a non-finite entry, for one) is
+    recomputed by ``np.linalg.svd`` from its own downloaded triangle and counted in ``device_singular_value_fallbacks``.
+    Above 128 columns the kernel does not serve: all triangles come down and :func:`singular_values_batch` runs.
+    ``return_status``: ``(sigma, sweeps, fallbacks)`` with the sweeps per matrix (None on the host route)."""
+    global device_singular_value_fallbacks
+    import numpy as np
+    from . import _lib
+    if r > _lib.SINGULAR_VALUES_MAX_R:
+        s = singular_values_batch(np.triu(d_R.to_host()[:B * r * r].reshape(B, r, r)))
+        return (s, None, 0) if return_status else s
+    d_sigma = _lib.DeviceArray((B * r,), np.float64)
+    d_status = _lib.DeviceArray((2 * B,), np.int32)
+    _lib.singular_values_batch(d_R, B, r, r * r, max_sweeps, d_sigma, r, d_status)
+    sigma = d_sigma.to_host().reshape(B, r)
+    status = d_status.to_host().reshape(B, 2)
+    failed = np.flatnonzero(status[:, 1] == 0)
+    for b in failed:
+        tri = np.empty((r, r))
+        _lib.check(_lib.load().figh_memcpy_d2h(tri.ctypes.data, d_R.ptr + 8 * int(b) * r * r, tri.nbytes))
+        tri = np.triu(tri)
+        sigma[b] = np.linalg.svd(tri, compute_uv=False) if np.isfinite(tri).all() else np.nan
+    device_singular_value_fallbacks += len(failed)
+    sigma = -np.sort(-sigma, axis=1)
+    return (sigma, status[:, 0].copy(), len(failed)) if return_status else sigma
+
+
 def relative_percent(sigma, phi):
     """100 sigma_i / |phi_i| rounded to two decimals -- the reference's std% (identification_tools.py:226-232,
     examples/staubli_TX40/identification.py:342-346).  An estimate that rounds to exactly zero (the scripts round phi to six

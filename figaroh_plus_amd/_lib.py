@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # FIGH_LIB_PATH: another build of the same ABI (same-box A/B of kernel variants); default is the in-tree library
 LIB_PATH = os.environ.get("FIGH_LIB_PATH") or os.path.join(_HERE, "libfigh.so")
 
-ABI_VERSION = 114  # include/figh.h FIGH_ABI_VERSION: load() refuses a library of another ABI
+ABI_VERSION = 115  # include/figh.h FIGH_ABI_VERSION: load() refuses a library of another ABI
 
 FIGH_OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_ALLOC, ERR_UNSUPPORTED, ERR_COMM = -1, -2, -3, -4, -5
@@ -129,6 +129,10 @@ SIGNATURES = {
     "figh_collision_distances": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, _c_int32_p, C.c_void_p, C.c_int64, C.c_int,
                                            _c_int32_p, _c_int32_p, _c_double_p, _c_double_p, C.c_int, _c_int32_p, C.c_double,
                                            C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "figh_difference_quotients": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                            C.c_int64]),
+    "figh_singular_values_batch": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
+                                             C.c_void_p]),
     "figh_kinematic_regressor": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, _c_double_p, C.c_int,
                                            _c_double_p, _c_int32_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
                                            C.c_int64, C.c_void_p, C.c_void_p]),
@@ -584,6 +588,21 @@ def collision_distances(model, B, n_per, idx, q_ptr, ldq, kind, parent, placemen
                                           placement.ctypes.data_as(_c_double_p), dims.ctypes.data_as(_c_double_p),
                                           len(pairs) // 2, pairs.ctypes.data_as(_c_int32_p), float(tol), int(max_iter),
                                           _ptr(out_ptr), ld_b, _ptr(witness_ptr), _ptr(status_ptr)))
+
+
+def difference_quotients(C_ptr, ldc, n_con, n_var, scheme, dx_ptr, J_ptr, ldj):
+    """figh_difference_quotients on raw device addresses: J[i, j] = (C[1 + j, i] - C[0 or 1 + n_var + j, i]) / dx[j]."""
+    check(load().figh_difference_quotients(_ptr(C_ptr), ldc, n_con, n_var, scheme, _ptr(dx_ptr), _ptr(J_ptr), ldj))
+
+
+SINGULAR_VALUES_MAX_R = 128  # csrc/figh_singular.hip kMaxR: above it figh_singular_values_batch answers ERR_UNSUPPORTED
+SINGULAR_VALUES_WGS_PER_CU = 8  # csrc/figh_singular.hip kMaxWgsPerCu: its grid has at most that many workgroups per CU
+
+
+def singular_values_batch(R_ptr, B, r, stride, max_sweeps, sigma_ptr, ld_sigma, status_ptr):
+    """figh_singular_values_batch on raw device addresses: sigma[b, :r] unordered, status[b] = (sweeps, converged)."""
+    check(load().figh_singular_values_batch(_ptr(R_ptr), B, r, stride, max_sweeps, _ptr(sigma_ptr), ld_sigma,
+                                            _ptr(status_ptr)))
 
 
 def kinematic_regressor(model, N, q_ptr, ldq, end_joint, end_placement, start_joint, start_placement, support, meas_mask,

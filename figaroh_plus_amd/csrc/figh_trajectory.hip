@@ -154,6 +154,41 @@ __global__ __launch_bounds__(256) void excitation_constraints_kernel(const Const
     }
 }
 
+// The constraint Jacobian by difference quotients: J[i][j] = (C[hi_j][i] - C[lo_j][i]) / dx[j] with hi_j = 1 + j and lo_j =
+// 0 (2-point) or 1 + n_var + j (3-point) -- one subtraction and one IEEE division, as NumPy rounds them.  A transposing
+// kernel: a workgroup stages a tile of 32 rows of J x 32 stencil rows through LDS; C is read with consecutive lanes along i
+// (runs of 32 doubles of one stencil row), J is written with consecutive lanes along j (runs of up to 32 doubles of one
+// row of J).  The tile's rows are 33 doubles apart: lanes along i write 66 banks apart, lanes along j read neighbours.
+// Tiles are walked by a capped grid; every address is formed in 64 bits; nothing outside [n_con, n_var) is touched.
+constexpr int kDqTile = 32;
+__global__ __launch_bounds__(256) void difference_quotients_kernel(const double *__restrict__ C, const long ldc, const long n_con,
+                                                                   const int n_var, const int three_point,
+                                                                   const double *__restrict__ dx, double *__restrict__ J,
+                                                                   const long ldj) {
+    __shared__ double tile[kDqTile][kDqTile + 1];
+    const int fast = threadIdx.x & 31, slow = threadIdx.x >> 5;  // 32 x 8 threads, four passes over the tile
+    const long tiles_i = (n_con + kDqTile - 1) / kDqTile, tiles_j = (n_var + kDqTile - 1) / kDqTile;
+    for (long t = blockIdx.x; t < tiles_i * tiles_j; t += gridDim.x) {
+        const long i0 = (t / tiles_j) * kDqTile;
+        const int j0 = (int)(t % tiles_j) * kDqTile;
+        for (int k = 0; k < kDqTile; k += 8) {
+            const long i = i0 + fast;
+            const int j = j0 + slow + k;
+            if (i < n_con && j < n_var) {
+                const long lo = three_point ? 1 + (long)n_var + j : 0;
+                tile[fast][slow + k] = (C[(1 + (long)j) * ldc + i] - C[lo * ldc + i]) / dx[j];
+            }
+        }
+        __syncthreads();
+        for (int k = 0; k < kDqTile; k += 8) {
+            const long i = i0 + slow + k;
+            const int j = j0 + fast;
+            if (i < n_con && j < n_var) J[i * ldj + j] = tile[slow + k][fast];
+        }
+        __syncthreads();
+    }
+}
+
 // The active joints as columns.  FIGH_ERR_UNSUPPORTED for a joint that is not one revolute or prismatic degree of freedom,
 // FIGH_ERR_INVALID for an index pair that is no joint of the model or is listed twice.
 int check_active_joints(const DevModel &m, const int n_act, const int32_t *idxq, const int32_t *idxv) {
@@ -254,6 +289,21 @@ extern "C" int figh_excitation_constraints(figh_model_t model, int64_t B, int64_
     hipLaunchKernelGGL(excitation_constraints_kernel, dim3(capped_grid(n_con, 256, kMaxGrid), capped_grid_rows(B)), dim3(256),
                        0, stream(), P, (long)B, (long)n_per, n_idx, d_idx, d_q, (long)ldq, d_v, (long)ldv, d_tau, d_out,
                        (long)ld_out);
+    FIGH_HIP(hipGetLastError());
+    return FIGH_OK;
+}
+
+extern "C" int figh_difference_quotients(const double *d_C, int64_t ldc, int64_t n_con, int n_var, int scheme,
+                                         const double *d_dx, double *d_J, int64_t ldj) {
+    if (int rc = ensure_device()) return rc;
+    FIGH_REQUIRE(d_C && d_dx && d_J, "NULL pointer");
+    FIGH_REQUIRE(scheme == 2 || scheme == 3, "difference quotients: the scheme is 2 (forward) or 3 (central)");
+    FIGH_REQUIRE(n_var >= 1 && n_con >= 1, "difference quotients: n_var and n_con must be at least 1");
+    FIGH_REQUIRE(ldc >= n_con && ldj >= n_var, "leading dimension below the width");
+    const long tiles = ((long)(n_con + kDqTile - 1) / kDqTile) * ((n_var + kDqTile - 1) / kDqTile);
+    ProfileScope scope("difference_quotients");
+    hipLaunchKernelGGL(difference_quotients_kernel, dim3(capped_grid(tiles, 1, kMaxGrid)), dim3(256), 0, stream(), d_C, (long)ldc,
+                       (long)n_con, n_var, scheme == 3 ? 1 : 0, d_dx, d_J, (long)ldj);
     FIGH_HIP(hipGetLastError());
     return FIGH_OK;
 }

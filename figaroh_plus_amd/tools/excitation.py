@@ -10,12 +10,13 @@ The reference evaluates, thousands of times per Ipopt solve (examples/tiago/opti
 The singular values of W_b are those of its R factor, and the R factor of a row-stacked matrix is the R factor of the
 stacked triangles, so neither W nor W_b is ever stored: one streamed K1 -> TSQR pass over the trajectory samples
 (``figh_regressor_tsqr``) gives an r x r triangle, ``figh_tsqr_merge`` folds in the triangle of the previous
-trajectories, and the r x r SVD runs on the host.
+trajectories, and the r x r SVD runs on the host or, batched and for r <= 128, on the device (``figh_singular_values_batch``).
+:class:`ExcitationProblem` at the end of this module is the optimiser's object on top of it all.
 """
 import numpy as np
 
 from .. import _lib
-from .._host import host_tail, singular_values_batch
+from .._host import host_tail, single_threaded_blas, singular_values_batch, singular_values_batch_device
 from . import regressor
 from .regressor import _samples_to_device, regressor_flags
 
@@ -89,6 +90,31 @@ def base_regressor_triangles_batch(robot, trajectories, param, idx_e, idx_base, 
     whatever B is (``figh_regressor_tsqr_batch_fused``).  Everything else goes through ``figh_regressor_tsqr_batch``: more
     than 80 base columns (TIAGo, TALOS) in one K1 launch over all samples, one batched TSQR launch and the pair-merge
     levels; up to 80 columns (TX40 with its coupling columns, short trajectories) trajectory by trajectory."""
+    d_R, B, r = _base_regressor_triangles_device(robot, trajectories, param, idx_e, idx_base, R_stack, coupling)
+    return np.triu(d_R.to_host().reshape(B, r, r))
+
+
+def _stack_to_device(R_stack, r):
+    """The triangle of the previous trajectories as the batched TSQR entries take it, or None."""
+    if R_stack is None:
+        return None
+    R_stack = np.ascontiguousarray(R_stack, dtype=np.float64)
+    if R_stack.shape != (r, r):
+        raise ValueError("R_stack must be the %d x %d triangle of the previous base regressor" % (r, r))
+    return _lib.DeviceArray.from_host(np.triu(R_stack).reshape(-1))
+
+
+def _triangles_into(dm, mode, flags, ft_mask, B, n_per, d_q, d_v, d_a, d_idx, r, d_stack, d_R):
+    """The B triangles of resident samples into ``d_R``: the fused chain launch where it serves, the batched TSQR elsewhere."""
+    fused = (mode == _lib.MODE_JOINT_TORQUE and dm.is_chain()
+             and _lib.regressor_tsqr_batch_fused(dm, flags, B, n_per, d_q, d_v, d_a, d_idx, r, d_stack, d_R))
+    if not fused:  # (ERR_UNSUPPORTED: nothing was launched)
+        _lib.regressor_tsqr_batch(dm, mode, flags, ft_mask, B, n_per, d_q, d_v, d_a, d_idx, r, d_stack, d_R)
+
+
+def _base_regressor_triangles_device(robot, trajectories, param, idx_e, idx_base, R_stack=None, coupling=False):
+    """``(d_R, B, r)``: the triangles of :func:`base_regressor_triangles_batch` where the kernels leave them -- B r x r
+    matrices back to back whose strict lower part is undefined."""
     if len(trajectories) == 0:
         raise ValueError("no trajectory given")
     mode, flags, ft_mask = regressor_flags(param, coupling)
@@ -98,25 +124,25 @@ def base_regressor_triangles_batch(robot, trajectories, param, idx_e, idx_base, 
     r = len(cols)
     B, n_per, d_q, d_v, d_a = _batch_to_device(robot, trajectories)
     d_idx = _lib.DeviceArray.from_host(cols)
-    d_stack = None
-    if R_stack is not None:
-        R_stack = np.ascontiguousarray(R_stack, dtype=np.float64)
-        if R_stack.shape != (r, r):
-            raise ValueError("R_stack must be the %d x %d triangle of the previous base regressor" % (r, r))
-        d_stack = _lib.DeviceArray.from_host(np.triu(R_stack).reshape(-1))
+    d_stack = _stack_to_device(R_stack, r)
     d_R = _lib.DeviceArray((B * r * r,), np.float64)
-    fused = (mode == _lib.MODE_JOINT_TORQUE and dm.is_chain()
-             and _lib.regressor_tsqr_batch_fused(dm, flags, B, n_per, d_q, d_v, d_a, d_idx, r, d_stack, d_R))
-    if not fused:  # (ERR_UNSUPPORTED: nothing was launched)
-        _lib.regressor_tsqr_batch(dm, mode, flags, ft_mask, B, n_per, d_q, d_v, d_a, d_idx, r, d_stack, d_R)
-    return np.triu(d_R.to_host().reshape(B, r, r))
+    _triangles_into(dm, mode, flags, ft_mask, B, n_per, d_q, d_v, d_a, d_idx, r, d_stack, d_R)
+    return d_R, B, r
 
 
 @host_tail
-def objective_cond_batch(robot, trajectories, param, idx_e, idx_base, R_stack=None, coupling=False):
+def objective_cond_batch(robot, trajectories, param, idx_e, idx_base, R_stack=None, coupling=False, singular_values="host"):
     """``[np.linalg.cond(W_b) for every trajectory]``: the objective of examples/tiago/optimal_trajectory.py:100-133 at
     the B perturbed trajectories of one finite-difference gradient (numdifftools around ``objective_func``, :296-313),
-    r x r SVDs batched on the host."""
+    r x r SVDs batched on the host.  ``singular_values="device"``: the triangles stay where they are and
+    ``figh_singular_values_batch`` (one-sided Jacobi, ``_host.singular_values_batch_device``) sends back B r singular
+    values; above 128 base columns that function takes the host route by itself."""
+    if singular_values == "device":
+        d_R, B, r = _base_regressor_triangles_device(robot, trajectories, param, idx_e, idx_base, R_stack, coupling)
+        s = singular_values_batch_device(d_R, B, r)
+        return (s.max(axis=1) / s.min(axis=1)).tolist()
+    if singular_values != "host":
+        raise ValueError("singular_values is 'host' or 'device', got %r" % (singular_values,))
     R = base_regressor_triangles_batch(robot, trajectories, param, idx_e, idx_base, R_stack, coupling)
     s = singular_values_batch(R)
     return (s.max(axis=1) / s.min(axis=1)).tolist()
@@ -495,3 +521,225 @@ def evaluate_waypoints_batch(robot, spline, freq, tps, X_batch, vel_wps, acc_wps
     if collision is None:
         return conds, constraints_batch(spline, batch, d_tau, tps)
     return conds, constraints_batch(spline, batch, d_tau, tps, collision)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The Ipopt problem of the same script (Problem_cond_Wb, examples/tiago/optimal_trajectory.py:246-330): objective, gradient,
+# constraints and jacobian of one X from ONE pass over the finite-difference stencil.
+SCHEMES = {"2-point": 2, "3-point": 3}
+
+
+def finite_difference_steps(x, scheme="2-point", rel_step=None):
+    """``(h, dx)`` of SciPy's rules (scipy.optimize._numdiff without bounds): h = rel_step sign(x) max(1, |x|), sign(0) = 1,
+    rel_step = sqrt(eps) for the 2-point and eps^(1/3) for the 3-point scheme; ``dx`` is the step as the arithmetic took
+    it, (x + h) - x or (x + h) - (x - h) -- what ``calibration_tools.fkm_jacobian_2point`` divides by as well."""
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    if scheme not in SCHEMES:
+        raise ValueError("scheme is '2-point' or '3-point', got %r" % (scheme,))
+    eps = np.finfo(np.float64).eps
+    if rel_step is None:
+        rel_step = eps ** 0.5 if scheme == "2-point" else eps ** (1 / 3)
+    h = rel_step * ((x >= 0).astype(np.float64) * 2 - 1) * np.maximum(1.0, np.abs(x))
+    dx = (x + h) - x if scheme == "2-point" else (x + h) - (x - h)
+    return h, dx
+
+
+def finite_difference_stencil(x, h, scheme="2-point"):
+    """The rows at which one finite-difference gradient evaluates: row 0 is x, row 1 + j is x + h_j e_j and, for the 3-point
+    scheme, row 1 + n + j is x - h_j e_j -- the row order of ``figh_difference_quotients``."""
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    n = len(x)
+    sign = np.concatenate((np.zeros((1, n)), np.eye(n)) + ((-np.eye(n),) if scheme == "3-point" else ()))
+    return np.where(sign == 0, x, x + sign * h)
+
+
+def difference_quotients(C, dx, scheme="2-point"):
+    """NumPy statement of ``figh_difference_quotients``: the (n_con, n_var) array ``(C[1 + j] - C[0]) / dx[j]`` (2-point) or
+    ``(C[1 + j] - C[1 + n_var + j]) / dx[j]`` (3-point) from the rows of :func:`finite_difference_stencil`."""
+    C, dx = np.asarray(C, dtype=np.float64), np.asarray(dx, dtype=np.float64).reshape(-1)
+    n = len(dx)
+    C = C.reshape(C.shape[0], -1)
+    if C.shape[0] != (1 + n if SCHEMES[scheme] == 2 else 1 + 2 * n):
+        raise ValueError("%d rows for %d variables and the %s scheme" % (C.shape[0], n, scheme))
+    lo = C[0] if SCHEMES[scheme] == 2 else C[1 + n:]
+    return np.ascontiguousarray(((C[1:1 + n] - lo) / dx[:, None]).T)
+
+
+class ExcitationProblem:
+    """``Problem_cond_Wb`` of examples/tiago/optimal_trajectory.py:246-330 -- ``objective(X)``, ``gradient(X)``,
+    ``constraints(X)``, ``jacobian(X)``, ``hessian(...) -> False`` -- with the finite differences of the reference (nd.Gradient
+    / nd.Jacobian around the objective and the constraints, :308-327) taken over ONE device pass: the stencil of
+    :func:`finite_difference_stencil` goes up as waypoints (B = n_var + 1 or 2 n_var + 1 rows), the B trajectories are sampled,
+    factored and constrained on the device, and what comes back is B r singular values with their status, the (n_con, n_var)
+    Jacobian (``figh_difference_quotients``) and row 0 of the constraints; neither the B x n_con rows nor the B triangles cross
+    the bus.  ``bounds()`` is get_bounds (:191-199), ``constraint_bounds()`` get_constr_value (:202-243).
+
+    Ipopt calls all four methods at one X: a *derivative pass* (the whole stencil) serves the four, a *value pass* (B = 1)
+    serves objective and constraints at a line-search point; both are cached on the bytes of X.  An X that no cached pass
+    holds costs a value pass when objective or constraints ask first and a derivative pass when gradient or jacobian do;
+    the very first evaluation of the object is a derivative pass whoever asks (an optimiser starts at an iterate, not at a
+    trial point).  What does not change during
+    a run stays on the device across calls: q0, the velocity and acceleration waypoints, the base-column list, R_stack and the
+    standard parameters.  The time points, the active-joint and waypoint-sample index lists and the collision geometry table
+    are host arguments of their entries and go with every call.
+
+    Steps are SciPy's (:func:`finite_difference_steps`); numdifftools' Richardson extrapolation is not mirrored.
+
+    Noise.  A finite-difference gradient of cond(W_b) is as good as the condition numbers are reproducible.  On either route
+    (``singular_values="device"``: one-sided Jacobi on the resident triangles; ``"host"``: LAPACK on the downloaded ones)
+    sigma_min carries a relative error of the order r 2^-53 cond, and the triangles themselves are reproduced only to
+    rounding on the fused chain path, so a quotient with step h has noise of the order r 2^-53 cond^2 / h: 3e-3 per
+    gradient entry at r = 40, cond = 100 and h = 1.5e-8.  Hence ``rel_step`` is a parameter, and the 3-point scheme's larger
+    default step (6e-6) is the quieter one.  The device route falls back to the host per matrix where the kernel did not converge
+    (``last_pass.host_fallbacks``)."""
+
+    def __init__(self, robot, spline, freq, tps, vel_wps, acc_wps, wp_init, param, idx_e, idx_base, R_stack=None,
+                 collision=None, scheme="2-point", rel_step=None, singular_values="device"):
+        if scheme not in SCHEMES:
+            raise ValueError("scheme is '2-point' or '3-point', got %r" % (scheme,))
+        if singular_values not in ("device", "host"):
+            raise ValueError("singular_values is 'host' or 'device', got %r" % (singular_values,))
+        self.robot, self.spline, self.freq, self.collision = robot, spline, freq, collision
+        self.scheme, self.rel_step, self.singular_values = scheme, rel_step, singular_values
+        self.tps = np.asarray(tps, dtype=np.float64).reshape(-1)
+        self.n_act, self.n_wps = spline.dim_q
+        if len(self.tps) != self.n_wps:
+            raise ValueError("%d time points for %d waypoints" % (len(self.tps), self.n_wps))
+        self.n_var = (self.n_wps - 1) * self.n_act
+        self.wp_init = np.asarray(wp_init, dtype=np.float64).reshape(-1)
+        vel, acc = (np.ascontiguousarray(x, dtype=np.float64) for x in (vel_wps, acc_wps))
+        if vel.shape != spline.dim_v or acc.shape != spline.dim_v:
+            raise ValueError("velocity / acceleration waypoints must be (%d, %d)" % spline.dim_v)
+        spline._check(np.zeros(spline.dim_q), vel, acc)
+        self.delta_t, self.T, self.n_per, t, _, _ = spline_times(freq, self.tps)
+        self.t = t.reshape(-1, 1)
+        self.idx_waypoints = waypoint_sample_indices(t, self.tps)
+        self.n_pairs = 0 if collision is None else len(collision.gmodel.collisionPairs)
+        self.n_dist = len(self.idx_waypoints) * self.n_pairs
+        self.n_con = len(self.idx_waypoints) * self.n_act + 2 * self.n_per * self.n_act + self.n_dist
+        # the two regressor calls of a pass: the base regressor's triangle, and rnea as W . phi of the rigid-body columns
+        self._dm = robot.device_model()
+        self._tri = regressor_flags(param, False)
+        _, ncols = self._dm.shape(*self._tri[:2])
+        cols = base_columns(ncols, idx_e, idx_base)
+        self.r = len(cols)
+        self._rigid = _rigid_body_param(param)
+        self._tau = regressor_flags(self._rigid, False)
+        _, ncols_tau = self._dm.shape(*self._tau[:2])
+        self._phi = np.array(list(robot.get_standard_parameters(self._rigid).values()), dtype=np.float64)
+        # resident across calls
+        self._d_idx = _lib.DeviceArray.from_host(cols)
+        self._d_stack = _stack_to_device(R_stack, self.r)
+        self._d_vel, self._d_acc = _lib.DeviceArray.from_host(vel.reshape(-1)), _lib.DeviceArray.from_host(acc.reshape(-1))
+        self._d_q0 = _lib.DeviceArray.from_host(np.ascontiguousarray(robot.q0, dtype=np.float64))
+        self._d_phi = _lib.DeviceArray.from_host(regressor.expand_parameters(self._phi, ncols_tau))
+        self._buffers = {}  # B -> the pass buffers (two sizes in a run: 1 and the stencil)
+        self._value = self._derivative = None  # (bytes of X, pass result)
+        self.last_pass = None
+        self.value_passes = self.derivative_passes = 0
+
+    # ------------------------------------------------------------------------------------------------ the reference's methods
+    def objective(self, X):
+        return float(self._values_at(X).conds[0])
+
+    def constraints(self, X):
+        return self._values_at(X).c0
+
+    def gradient(self, X):
+        p = self._derivatives_at(X)
+        n = self.n_var
+        lo = p.conds[0] if self.scheme == "2-point" else p.conds[1 + n:]
+        return (p.conds[1:1 + n] - lo) / p.dx
+
+    def jacobian(self, X):
+        return self._derivatives_at(X).jacobian
+
+    def hessian(self, X=None, lagrange=None, obj_factor=None):
+        return False
+
+    def bounds(self):
+        """``(lb, ub)`` of get_bounds (:191-199): the position limits of the active joints per waypoint behind the first."""
+        lb, ub = [], []
+        for _ in range(1, self.n_wps):
+            lb.extend(self.spline.lower_q)
+            ub.extend(self.spline.upper_q)
+        return lb, ub
+
+    def constraint_bounds(self, margin=0.01):
+        return constraint_bounds(self.spline, self.n_wps, self.n_per, self.n_pairs, margin)
+
+    # ------------------------------------------------------------------------------------------------------------ the passes
+    def _key(self, X):
+        X = np.ascontiguousarray(X, dtype=np.float64).reshape(-1)
+        if X.size != self.n_var:
+            raise ValueError("X has %d entries, the problem %d search variables" % (X.size, self.n_var))
+        return X.tobytes()
+
+    def _values_at(self, X):
+        key = self._key(X)
+        for cached in (self._derivative, self._value):
+            if cached is not None and cached[0] == key:
+                return cached[1]
+        if self._derivative is None:  # the first point of a run is an iterate, whose derivatives are asked for next
+            return self._derivatives_at(X)
+        self._value = (key, self._pass(np.frombuffer(key, dtype=np.float64).reshape(1, -1), None))
+        self.value_passes += 1
+        return self._value[1]
+
+    def _derivatives_at(self, X):
+        key = self._key(X)
+        if self._derivative is None or self._derivative[0] != key:
+            x = np.frombuffer(key, dtype=np.float64)
+            h, dx = finite_difference_steps(x, self.scheme, self.rel_step)
+            self._derivative = (key, self._pass(finite_difference_stencil(x, h, self.scheme), dx))
+            self.derivative_passes += 1
+        return self._derivative[1]
+
+    def _pass_buffers(self, B):
+        from ..device import GpuMatrix
+        if B not in self._buffers:
+            m = self.spline.rmodel
+            q, v, a = (GpuMatrix.empty(B * self.n_per, w) for w in (m.nq, m.nv, m.nv))
+            self._buffers[B] = (q, v, a, _lib.DeviceArray((B * self.r * self.r,), np.float64),
+                                _lib.DeviceArray((m.nv * B * self.n_per,), np.float64),
+                                _lib.DeviceArray((B * self.n_con,), np.float64),
+                                _lib.DeviceArray((self.n_con * self.n_var,), np.float64) if B > 1 else None,
+                                _lib.DeviceArray((self.n_con,), np.float64) if B > 1 else None)
+        return self._buffers[B]
+
+    def _pass(self, Xs, dx):
+        """One pass over the rows ``Xs`` (B, n_var); ``dx`` None: a value pass."""
+        from types import SimpleNamespace
+        B = Xs.shape[0]
+        sp, dm, n_per, r, n_con = self.spline, self._dm, self.n_per, self.r, self.n_con
+        q, v, a, d_R, d_tau, d_C, d_J, d_c0 = self._pass_buffers(B)
+        d_wps = _lib.DeviceArray.from_host(waypoints_from_search_variables(Xs, self.wp_init, self.n_wps, self.n_act).reshape(-1))
+        _lib.spline_sample(dm, B, self.n_wps, n_per, self.freq, sp.act_idxq, sp.act_idxv, self.tps, d_wps, self._d_vel, 0,
+                           self._d_acc, 0, self._d_q0, q.ptr, q.ld, v.ptr, a.ptr, v.ld)
+        mode, flags, ft_mask = self._tri
+        _triangles_into(dm, mode, flags, ft_mask, B, n_per, q.buf, v.buf, a.buf, self._d_idx, r, self._d_stack, d_R)
+        if self.singular_values == "device":
+            s, sweeps, fallbacks = singular_values_batch_device(d_R, B, r, return_status=True)
+        else:
+            with single_threaded_blas():
+                s, sweeps, fallbacks = singular_values_batch(np.triu(d_R.to_host().reshape(B, r, r))), None, 0
+        conds = s.max(axis=1) / s.min(axis=1)
+        mode, flags, ft_mask = self._tau
+        if not _lib.regressor_apply(dm, mode, flags, ft_mask, B * n_per, q.buf, v.buf, a.buf, self._d_phi, d_tau):
+            d_tau = regressor.regressor_times_parameters_device(self.robot, q.buf, v.buf, a.buf, B * n_per, self._rigid, self._phi)
+        _lib.excitation_constraints(dm, B, n_per, sp.act_idxq, sp.act_idxv, self.idx_waypoints, q.ptr, q.ld, v.ptr, v.ld, d_tau,
+                                    d_C.ptr, n_con)
+        if self.n_dist:
+            from . import robotcollisions as rc
+            rc.collision_distances_device(self.robot, self.collision.gmodel, q.ptr, q.ld, B, n_per, self.idx_waypoints,
+                                          d_C.ptr + 8 * (n_con - self.n_dist), n_con, self.collision.tol, self.collision.max_iter)
+        if dx is None:
+            c0, jac = d_C.to_host(), None
+        else:
+            d_dx = _lib.DeviceArray.from_host(dx)
+            _lib.difference_quotients(d_C, n_con, n_con, self.n_var, SCHEMES[self.scheme], d_dx, d_J, self.n_var)
+            _lib.check(_lib.load().figh_memcpy_d2d(d_c0.ptr, d_C.ptr, 8 * n_con))  # row 0 alone comes down
+            c0, jac = d_c0.to_host(), d_J.to_host().reshape(n_con, self.n_var)
+        self.last_pass = SimpleNamespace(B=B, conds=conds, dx=dx, sweeps=sweeps, host_fallbacks=fallbacks, sigma=s, c0=c0,
+                                         jacobian=jac)
+        return self.last_pass

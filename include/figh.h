@@ -91,7 +91,7 @@ typedef struct figh_model_s *figh_model_t;
  * (round 5 did so for figh_tsqr_selected_wrench / figh_regressor_build_padded without a bump: a library of the older ABI
  * accepts the longer argument list under cdecl and silently ignores the new arguments).  figaroh_plus_amd/_lib.py refuses a
  * library -- in-tree or FIGH_LIB_PATH -- whose figh_version() differs from the value it was written against. */
-#define FIGH_ABI_VERSION 114
+#define FIGH_ABI_VERSION 115
 int figh_version(void);
 const char *figh_last_error(void);
 int figh_device_count(int *count);
@@ -599,6 +599,34 @@ int figh_collision_distances(figh_model_t model, int64_t B, int64_t n_per, int n
                              const double *d_q, int64_t ldq, int n_geom, const int32_t *h_kind, const int32_t *h_parent,
                              const double *h_placement, const double *h_dims, int n_pairs, const int32_t *h_pairs, double tol,
                              int max_iter, double *d_out, int64_t ld_b, double *d_witness, int32_t *d_status);
+
+/* figh_difference_quotients: the constraint Jacobian of the same problem by finite differences (the reference takes
+ * nd.Jacobian around constraints, examples/tiago/optimal_trajectory.py:321-327) from the constraint rows that
+ * figh_excitation_constraints and figh_collision_distances leave.  d_C: the rows of the stencil, ldc doubles apart: row 0 at
+ * X, row 1 + j at X + h_j e_j and, with scheme = 3, row 1 + n_var + j at X - h_j e_j.  d_dx: the n_var steps as the host
+ * re-read them ((x + h) - x, or (x + h) - (x - h) for scheme 3).  d_J[i ldj + j] = (C[1 + j][i] - C[0][i]) / dx[j] for
+ * scheme = 2 and (C[1 + j][i] - C[1 + n_var + j][i]) / dx[j] for scheme = 3: one subtraction and one IEEE division,
+ * bit-equal to the NumPy statement; the dense row-major (n_con, n_var) Jacobian that Ipopt takes, nothing outside
+ * [n_con, n_var) of a padded d_J is touched.  FIGH_ERR_INVALID (nothing launched): scheme not 2 or 3, n_var < 1, n_con < 1,
+ * ldc < n_con, ldj < n_var.  Without a HIP device: FIGH_ERR_NO_DEVICE, before any argument is looked at. */
+int figh_difference_quotients(const double *d_C, int64_t ldc, int64_t n_con, int n_var, int scheme, const double *d_dx,
+                              double *d_J, int64_t ldj);
+
+/* figh_singular_values_batch: the singular values of B row-major r x r matrices, stride >= r r doubles apart, of which ONLY
+ * THE UPPER TRIANGLE IS READ (figh_regressor_tsqr_batch[_fused] leave the strict lower part undefined) -- the r x r SVDs of
+ * the batched condition-number objective (np.linalg.cond(W_b), examples/tiago/optimal_trajectory.py:100-133) without the
+ * download of the triangles.  One-sided (Hestenes) Jacobi on the columns in fp64 (csrc/figh_singular.hip states the
+ * rotation, its threshold 2^-52 sqrt(alpha beta) and the round-robin order; _host.jacobi_singular_values_mirror is the
+ * same statements in NumPy), one workgroup per matrix with the matrix in LDS.  d_sigma[b ld_sigma + k], k < r: the singular
+ * values of matrix b IN NO PARTICULAR ORDER; d_status[2 b]: the sweeps used, d_status[2 b + 1]: 1 when a sweep without a
+ * rotation ended the matrix, 0 when max_sweeps sweeps did (sigma is then unspecified: the caller recomputes that matrix;
+ * a matrix with a non-finite entry ends like this, it is no error of the call).  Every loop of the kernel is bounded by
+ * its arguments.  No atomics, plain stores: two calls give the same bits.
+ * FIGH_ERR_INVALID (nothing launched): r < 1, B < 1, stride < r r, ld_sigma < r, max_sweeps outside [1, 1000].
+ * FIGH_ERR_UNSUPPORTED (nothing launched): r > 128 (the matrix no longer fits the LDS of a compute unit).  Without a HIP
+ * device: FIGH_ERR_NO_DEVICE, before any argument is looked at. */
+int figh_singular_values_batch(const double *d_R, int64_t B, int r, int64_t stride, int max_sweeps, double *d_sigma,
+                               int64_t ld_sigma, int32_t *d_status);
 
 /* ------------------------------------------------------------------ geometric calibration
  * The kinematic regressor and the updated forward kinematics of src/figaroh/calibration/calibration_tools.py, over
