@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # FIGH_LIB_PATH: another build of the same ABI (same-box A/B of kernel variants); default is the in-tree library
 LIB_PATH = os.environ.get("FIGH_LIB_PATH") or os.path.join(_HERE, "libfigh.so")
 
-ABI_VERSION = 115  # include/figh.h FIGH_ABI_VERSION: load() refuses a library of another ABI
+ABI_VERSION = 116  # include/figh.h FIGH_ABI_VERSION: load() refuses a library of another ABI
 
 FIGH_OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_ALLOC, ERR_UNSUPPORTED, ERR_COMM = -1, -2, -3, -4, -5
@@ -120,6 +120,10 @@ SIGNATURES = {
     "figh_joint_difference": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
     "figh_gradient_cols": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
                                      C.c_int64]),
+    "figh_quat_log": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]),
+    "figh_rotvec_to_quat": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
+    "figh_wrench_transport": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int,
+                                        C.c_void_p, C.c_int]),
     "figh_spline_sample": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_double, _c_int32_p, _c_int32_p,
                                      _c_double_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]),
@@ -537,6 +541,26 @@ def joint_difference(model, N, q_ptr, ts, dt_ptr, dq_ptr):
 def gradient_cols(F_ptr, rows, cols, ld, ncols_active, h, h_ptr, G_ptr, ldg):
     """np.gradient(F[:, c], edge_order=1) / (h_ptr[row] or h) for c < ncols_active, +0.0 behind (figh_gradient_cols)."""
     check(load().figh_gradient_cols(F_ptr, rows, cols, ld, ncols_active, float(h), h_ptr, G_ptr, ldg))
+
+
+WRENCH_LAYOUTS = {"sample": 0, "stacked": 1}  # include/figh.h FIGH_WRENCH_SAMPLE / FIGH_WRENCH_STACKED
+
+
+def quat_log(quat_ptr, N, ld_quat, rotvec_ptr, ld_rotvec):
+    """rotvec[i] = log3 of the quaternion (x y z w) at quat_ptr + 8 i ld_quat (figh_quat_log), on raw device addresses."""
+    check(load().figh_quat_log(quat_ptr, N, ld_quat, rotvec_ptr, ld_rotvec))
+
+
+def rotvec_to_quat(rotvec_ptr, N, ld_rotvec, ref_ptr, ld_ref, out_ptr, ld_out):
+    """out[i] = +-quaternion of exp3(rotvec[i]), the sign chosen against ref[i] (figh_rotvec_to_quat); ``out_ptr`` may be
+    ``ref_ptr`` with the same leading dimension."""
+    check(load().figh_rotvec_to_quat(rotvec_ptr, N, ld_rotvec, ref_ptr, ld_ref, out_ptr, ld_out))
+
+
+def wrench_transport(model, joint, N, q_ptr, ldq, F_ptr, layout_in, inverse, out_ptr, layout_out):
+    """N wrenches through oMi[joint](q_i) (figh_wrench_transport); the layouts are keys of WRENCH_LAYOUTS."""
+    check(load().figh_wrench_transport(model.handle, int(joint), N, q_ptr, ldq, F_ptr, WRENCH_LAYOUTS[layout_in],
+                                       1 if inverse else 0, out_ptr, WRENCH_LAYOUTS[layout_out]))
 
 
 def spline_sample(model, B, n_wps, n_per, freq, act_idxq, act_idxv, tps, d_wps, d_vel_wps, vel_stride, d_acc_wps, acc_stride,

@@ -427,6 +427,308 @@ def low_pass_filter_data(data, param, nbutter=5):
     return out[nbord:out.shape[0] - nbord]
 
 
+# ----------------------------------------------------------------------------------------------------------
+# Free-flyer real data (examples/human/identification.py): the orientation filter (:330-374) and the wrench transport
+# (:434-453, :471-555) on the device (csrc/figh_freeflyer.hip).  Each device function has its NumPy mirror beside it: the
+# statements of the kernel element by element, in the kernel's operation order, with no BLAS product -- the function's
+# definition on the host, as ``joint_difference`` is for figh_joint_difference.  Quaternions are (x y z w), 6-vectors
+# (linear, angular).
+_SERIES_BELOW = 2.0 ** -13           # both series of csrc/figh_freeflyer.hip
+_KEEP_ABOVE = 0.7071067811865476     # cos(pi / 4): the reference's 2 acos(d) < pi / 2
+
+
+def _rows_2d(x, width, what):
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim == 1 and x.shape[0] == width:
+        x = x[None, :]
+    if x.ndim != 2 or x.shape[1] != width or x.shape[0] < 1:
+        raise ValueError("%s: expected (N, %d) with N >= 1, got shape %r" % (what, width, x.shape))
+    return x
+
+
+def quaternion_log_mirror(quat):
+    """figh_quat_log on the host: n = sqrt((x x + y y) + z z), r = sgn(w) (2 atan2(n, |w|) / n) (x, y, z) with sgn(0) = +1,
+    the series 2 ((1 - t^2 / 3) + t^4 / 5) / |w|, t = n / |w|, for n < 2^-13 |w|, three +0.0 for n = 0."""
+    quat = _rows_2d(quat, 4, "quaternion_log")
+    x, y, z, w = quat[:, 0], quat[:, 1], quat[:, 2], quat[:, 3]
+    n, aw = np.sqrt((x * x + y * y) + z * z), np.abs(w)
+    s = np.where(w < 0.0, -1.0, 1.0)
+    with np.errstate(all="ignore"):
+        t = n / aw
+        t2 = t * t
+        series = 2.0 * ((1.0 - t2 / 3.0) + (t2 * t2) / 5.0) / aw
+        f = np.where(n < _SERIES_BELOW * aw, series, 2.0 * np.arctan2(n, aw) / n)
+        sf = s * f
+        out = np.stack([sf * x, sf * y, sf * z], axis=1)
+    out[n == 0.0] = 0.0
+    return out
+
+
+def rotation_vector_to_quaternion_mirror(rotvec, quat_ref):
+    """figh_rotvec_to_quat on the host: the canonical quaternion of exp3(r), Eigen's representative of it, and the
+    reference's sign test against ``quat_ref`` (keep iff d > 0.7071067811865476; d > 1 by rounding keeps)."""
+    rotvec, ref = _rows_2d(rotvec, 3, "rotation_vector_to_quaternion"), _rows_2d(quat_ref, 4, "rotation_vector_to_quaternion")
+    if len(rotvec) != len(ref):
+        raise ValueError("rotation_vector_to_quaternion: %d rotation vectors, %d reference quaternions" % (len(rotvec), len(ref)))
+    rx, ry, rz = rotvec[:, 0], rotvec[:, 1], rotvec[:, 2]
+    th2 = (rx * rx + ry * ry) + rz * rz
+    th = np.sqrt(th2)
+    th4 = th2 * th2
+    with np.errstate(all="ignore"):
+        small = th < _SERIES_BELOW
+        a = np.where(small, (0.5 - th2 / 48.0) + th4 / 3840.0, np.sin(0.5 * th) / th)
+        c = np.where(small, (1.0 - th2 / 8.0) + th4 / 384.0, np.cos(0.5 * th))
+    q0, q1, q2 = a * rx, a * ry, a * rz
+    lead = q0.copy()
+    lead = np.where(np.abs(q1) > np.abs(lead), q1, lead)
+    lead = np.where(np.abs(q2) > np.abs(lead), q2, lead)
+    lead = np.where(np.abs(c) > 0.5, c, lead)
+    sE = np.where(lead < 0.0, -1.0, 1.0)
+    d = sE * (((q0 * ref[:, 0] + q1 * ref[:, 1]) + q2 * ref[:, 2]) + c * ref[:, 3])
+    sg = np.where(d > _KEEP_ABOVE, sE, -sE)
+    return np.stack([sg * q0, sg * q1, sg * q2, sg * c], axis=1)
+
+
+def _rot_rows(R, x, transpose=False):
+    """y = R x (R^T x), R (..., 3, 3), x a list of three arrays: three products summed left to right, like figh_spatial.h."""
+    if transpose:
+        return [R[..., 0, r] * x[0] + R[..., 1, r] * x[1] + R[..., 2, r] * x[2] for r in range(3)]
+    return [R[..., r, 0] * x[0] + R[..., r, 1] * x[1] + R[..., r, 2] * x[2] for r in range(3)]
+
+
+def _matmul3_rows(A, B):
+    """A B entry by entry, A (..., 3, 3) or (3, 3), B (N, 3, 3): matmul3 of figh_spatial.h."""
+    C = np.empty(B.shape)
+    for r in range(3):
+        for c in range(3):
+            C[:, r, c] = A[..., r, 0] * B[:, 0, c] + A[..., r, 1] * B[:, 1, c] + A[..., r, 2] * B[:, 2, c]
+    return C
+
+
+def _cross_rows(a, b):
+    return [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
+
+
+def _joint_id(model, joint):
+    j = model.getJointId(joint) if isinstance(joint, str) else int(joint)
+    if not 0 <= j < model.njoints:
+        raise ValueError("transport_wrench: joint %r is not in the model" % (joint,))
+    return j
+
+
+def joint_world_placement_mirror(model, q, joint):
+    """(R, p) = oMi[joint](q_i), (N, 3, 3) and (N, 3), as figh_wrench_transport composes it: root first,
+    (Rk, pk) = placement_j . M_j(q_j), (R, p) = (Rk, pk) at the first joint, then (R Rk, p + R pk)."""
+    from ..calibration.calibration_tools import _joint_motion
+
+    q = np.asarray(q, dtype=np.float64)
+    N = q.shape[0]
+    path, j = [], _joint_id(model, joint)
+    while j > 0:
+        path.append(j)
+        j = model.parents[j]
+    R = np.broadcast_to(np.eye(3), (N, 3, 3)).copy()
+    p = np.zeros((N, 3))
+    for s, j in enumerate(path[::-1]):
+        Rj, pj = _joint_motion(model.joints[j], q)
+        pl = model.jointPlacements[j]
+        Pr, Pt = np.asarray(pl.rotation, dtype=np.float64), np.asarray(pl.translation, dtype=np.float64)
+        Rk = _matmul3_rows(Pr, Rj)
+        pk = np.stack(_rot_rows(Pr, [pj[:, 0], pj[:, 1], pj[:, 2]]), axis=1) + Pt[None, :]
+        if s == 0:
+            R, p = Rk, pk
+        else:
+            t = _rot_rows(R, [pk[:, 0], pk[:, 1], pk[:, 2]])
+            R = _matmul3_rows(R, Rk)
+            p = p + np.stack(t, axis=1)
+    return R, p
+
+
+_WRENCH_LAYOUTS = ("sample", "stacked")
+
+
+def _check_layouts(layout_in, layout_out):
+    for name in (layout_in, layout_out):
+        if name not in _WRENCH_LAYOUTS:
+            raise ValueError("transport_wrench: unknown layout %r (one of %r)" % (name, _WRENCH_LAYOUTS))
+
+
+def _wrench_components(wrench, N, layout):
+    """The six component arrays (N,) of a host wrench array in ``layout``."""
+    w = np.asarray(wrench, dtype=np.float64)
+    if layout == "sample":
+        if w.shape != (N, 6):
+            raise ValueError("transport_wrench: the sample layout is (N, 6) = (%d, 6), got shape %r" % (N, w.shape))
+        return [w[:, k] for k in range(6)]
+    if w.reshape(-1).shape[0] != 6 * N or w.ndim != 1:
+        raise ValueError("transport_wrench: the stacked layout has 6 N = %d entries, got shape %r" % (6 * N, w.shape))
+    return [w[k * N:(k + 1) * N] for k in range(6)]
+
+
+def _as_samples(model, q):
+    q = np.asarray(q, dtype=np.float64)
+    if q.ndim != 2 or q.shape[1] != model.nq or q.shape[0] < 1:
+        raise ValueError("expected q of shape (N, nq = %d) with N >= 1, got %r" % (model.nq, q.shape))
+    return q
+
+
+def transport_wrench_mirror(model, q, wrench, joint="root_joint", inverse=False, layout_in="sample", layout_out="stacked"):
+    """figh_wrench_transport on the host.  ``inverse=False``: pin.Force.se3Action(oMi[joint]), f' = R f,
+    n' = R n + p x f'; ``inverse=True``: se3ActionInverse, f' = R^T f, n' = R^T (n - p x f)."""
+    _check_layouts(layout_in, layout_out)
+    q = _as_samples(model, q)
+    N = q.shape[0]
+    w = _wrench_components(wrench, N, layout_in)
+    R, p = joint_world_placement_mirror(model, q, _joint_id(model, joint))
+    f, n, pp = w[:3], w[3:], [p[:, 0], p[:, 1], p[:, 2]]
+    if inverse:
+        c = _cross_rows(pp, f)
+        m = [n[d] - c[d] for d in range(3)]
+        o = _rot_rows(R, f, transpose=True) + _rot_rows(R, m, transpose=True)
+    else:
+        fo = _rot_rows(R, f)
+        m = _rot_rows(R, n)
+        c = _cross_rows(pp, fo)
+        o = fo + [m[d] + c[d] for d in range(3)]
+    return np.stack(o, axis=1) if layout_out == "sample" else np.concatenate(o)
+
+
+def _device_rows(x, width, what):
+    """(GpuMatrix, was_resident) of an (N, width) host array or GpuMatrix."""
+    if isinstance(x, GpuMatrix):
+        if x.cols != width or x.rows < 1:
+            raise ValueError("%s: expected (N, %d) with N >= 1, got %r" % (what, width, x.shape))
+        return x, True
+    return GpuMatrix.from_host(_rows_2d(x, width, what)), False
+
+
+def quaternion_log(quat):
+    """``pin.log3(pin.Quaternion(quat[i]))`` of every row (examples/human/identification.py:330-339) on the device
+    (figh_quat_log): the principal rotation vector, (N, 3).  ``quat``: (N, 4) quaternions (x y z w), a host array (a host
+    array comes back) or a ``GpuMatrix`` of four columns with any leading dimension -- a window of q is
+    ``GpuMatrix(_DevView(q.buf, 8 * (idx_q + 3)), N, 4, q.ld)`` -- which gives a resident ``GpuMatrix``.  q and -q give the
+    same vector; where w changes sign at theta = pi the vector jumps as the reference's does (nothing unwraps it).
+    Host definition: :func:`quaternion_log_mirror`."""
+    Q, resident = _device_rows(quat, 4, "quaternion_log")
+    out = GpuMatrix.empty(Q.rows, 3)
+    _lib.quat_log(Q.ptr, Q.rows, Q.ld, out.ptr, 3)
+    return out if resident else out.numpy()
+
+
+def rotation_vector_to_quaternion(rotvec, quat_ref):
+    """``pin.Quaternion(pin.exp3(rotvec[i]))`` with the sign the script chooses against ``quat_ref[i]``
+    (examples/human/identification.py:349-364) on the device (figh_rotvec_to_quat), (N, 4).  The representative is Eigen's
+    (w > 0 when |w| > 1/2, else the largest vector component positive), kept when its dot product d with the reference
+    exceeds cos(pi / 4) and negated otherwise.  The one deliberate difference from the script: when rounding makes d > 1
+    its ``arccos`` is NaN and it negates; here that case keeps -- rounding noise decides it, and -q is the same rotation.
+    Host arrays in, host array out; a ``GpuMatrix`` rotvec gives a resident ``GpuMatrix``.
+    Host definition: :func:`rotation_vector_to_quaternion_mirror`."""
+    what = "rotation_vector_to_quaternion"
+    rotvec, quat_ref = (x if isinstance(x, GpuMatrix) else _rows_2d(x, w, what) for x, w in ((rotvec, 3), (quat_ref, 4)))
+    if len(rotvec) != len(quat_ref):
+        raise ValueError("%s: %d rotation vectors, %d reference quaternions" % (what, len(rotvec), len(quat_ref)))
+    Rv, resident = _device_rows(rotvec, 3, what)
+    Qr, _ = _device_rows(quat_ref, 4, what)
+    out = GpuMatrix.empty(Rv.rows, 4)
+    _lib.rotvec_to_quat(Rv.ptr, Rv.rows, Rv.ld, Qr.ptr, Qr.ld, out.ptr, 4)
+    return out if resident else out.numpy()
+
+
+def _free_flyers(model):
+    return [j for j in model.joints[1:] if j.jtype == 3]
+
+
+def filter_free_flyer_mirror(model, q, param, nbutter=5):
+    """:func:`filter_free_flyer` on the host: ``scipy.signal.filtfilt`` (what the reference's low_pass_filter_data calls) and
+    the mirrors of the logarithm and the exponential, with the same row pairing."""
+    from scipy import signal
+
+    q = _as_samples(model, q)
+    b, a = signal.butter(nbutter, param["ts"] * param["cut_off_frequency_butterworth"] / 2, "low")
+    padlen, nbord = 3 * (max(len(b), len(a)) - 1), 5 * nbutter
+
+    def low_pass(x):
+        y = signal.filtfilt(b, a, x, axis=0, padtype="odd", padlen=padlen)
+        return y[nbord:y.shape[0] - nbord]
+
+    q_f = np.ascontiguousarray(low_pass(q))
+    for j in _free_flyers(model):
+        lo = j.idx_q + 3
+        rotvec = low_pass(quaternion_log_mirror(q[:, lo:lo + 4]))
+        if len(rotvec):
+            q_f[:, lo:lo + 4] = rotation_vector_to_quaternion_mirror(rotvec, q[:len(rotvec), lo:lo + 4])
+    return q_f
+
+
+def filter_free_flyer(model, q, param, nbutter=5):
+    """The free-flyer orientation filter of examples/human/identification.py:330-374, resident from q to q: every column of
+    ``q`` goes through :func:`low_pass_filter_data`; for every free-flyer joint the rotation vector of its quaternion
+    (:func:`quaternion_log`) goes through it too, is turned back into a quaternion
+    (:func:`rotation_vector_to_quaternion`) and written over the filtered quaternion columns in place (``q_m[:, 3:7] =
+    quat_filt``).  Returns the filtered configurations, ``len(q) - 10 nbutter`` rows.
+
+    ROW PAIRING: the script's own.  ``low_pass_filter_data`` trims 5 nbutter rows at each border, so row ``ii`` of the
+    filtered signal is sample ``ii + 5 nbutter`` -- and the script chooses its sign against ``q_mocap[ii]``, the RAW row
+    ``ii``, not ``ii + 5 nbutter``.  A drop-in keeps that.
+
+    A host array comes back as a host array; a ``GpuMatrix`` (any leading dimension) stays in HBM and a ``GpuMatrix`` comes
+    back, ready for :func:`calculate_first_second_order_differentiation`.  Host definition:
+    :func:`filter_free_flyer_mirror`."""
+    resident = isinstance(q, GpuMatrix)
+    Q = q if resident else GpuMatrix.from_host(_as_samples(model, q))
+    if Q.cols != model.nq or Q.rows < 1:
+        raise ValueError("expected q of shape (N, nq = %d) with N >= 1, got %r" % (model.nq, Q.shape))
+    q_f = low_pass_filter_data(Q, param, nbutter)
+    for j in _free_flyers(model):
+        off = 8 * (j.idx_q + 3)
+        rotvec = GpuMatrix.empty(Q.rows, 3)
+        _lib.quat_log(Q.ptr + off, Q.rows, Q.ld, rotvec.ptr, 3)
+        rotvec_f = low_pass_filter_data(rotvec, param, nbutter)
+        if rotvec_f.rows:
+            _lib.rotvec_to_quat(rotvec_f.ptr, rotvec_f.rows, rotvec_f.ld, Q.ptr + off, Q.ld, q_f.ptr + off, q_f.ld)
+    return q_f if resident else q_f.numpy()
+
+
+def transport_wrench(model, q, wrench, joint="root_joint", inverse=False, layout_in="sample", layout_out="stacked"):
+    """A wrench per sample carried through ``oMi[joint](q_i)`` on the device (figh_wrench_transport).
+    ``inverse=True`` is ``pin.Force.se3ActionInverse`` -- the measured force-plate wrench from the world frame into the
+    pelvis frame, examples/human/identification.py:434-453 --, ``inverse=False`` is ``se3Action`` -- the simulated and
+    identified wrenches back to the world frame, :471-555.  ``joint``: a joint name or id, any joint of the model.
+
+    Layouts: "sample" is (N, 6), (linear, angular) per row; "stacked" is the vector ``[k N + i]``, the order of ``tau`` and of
+    ``regressor_times_parameters``.  Host arrays in, host array out.  A ``GpuMatrix`` q, a ``GpuMatrix`` wrench (sample layout) or
+    a device vector (stacked layout) gives a resident result with no download: a ``GpuMatrix`` (sample) or a ``DeviceArray``
+    (stacked), which ``IdentificationPipeline.set_samples(tau=...)`` takes as it is.
+    Host definition: :func:`transport_wrench_mirror`."""
+    _check_layouts(layout_in, layout_out)
+    j = _joint_id(model, joint)
+    wrench_resident = isinstance(wrench, GpuMatrix) or hasattr(wrench, "ptr")
+    resident = isinstance(q, GpuMatrix) or wrench_resident
+    if not isinstance(q, GpuMatrix):
+        q = _as_samples(model, q)
+    elif q.cols != model.nq or q.rows < 1:
+        raise ValueError("expected q of shape (N, nq = %d) with N >= 1, got %r" % (model.nq, q.shape))
+    N = len(q)
+    if wrench_resident:
+        if layout_in == "sample":
+            if not isinstance(wrench, GpuMatrix) or wrench.shape != (N, 6) or wrench.ld != 6:
+                raise ValueError("transport_wrench: a resident wrench in the sample layout is a dense GpuMatrix (%d, 6)" % N)
+        elif isinstance(wrench, GpuMatrix) or int(getattr(wrench, "size", 6 * N)) != 6 * N:
+            raise ValueError("transport_wrench: a resident wrench in the stacked layout is a device vector of 6 N = %d entries"
+                             % (6 * N))
+        d_F = wrench
+    else:
+        _wrench_components(wrench, N, layout_in)  # (the shape check)
+        d_F = _lib.DeviceArray.from_host(np.ascontiguousarray(wrench, dtype=np.float64).reshape(-1))
+    Q = q if isinstance(q, GpuMatrix) else GpuMatrix.from_host(q)
+    handle = _lib.ModelHandle(model.to_flat())
+    out = GpuMatrix.empty(N, 6) if layout_out == "sample" else _lib.DeviceArray((6 * N,), np.float64)
+    _lib.wrench_transport(handle, j, N, Q.ptr, Q.ld, d_F.ptr, layout_in, inverse, out.ptr, layout_out)
+    if resident:
+        return out
+    return out.numpy() if layout_out == "sample" else out.to_host()
+
+
 def _decimate_design(q, n=8):
     """The IIR of ``scipy.signal.decimate(ftype='iir')``: Chebyshev-I order 8, 0.05 dB, 0.8/q, as second-order
     sections, with SciPy's padlen rule for sosfiltfilt."""

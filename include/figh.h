@@ -91,7 +91,7 @@ typedef struct figh_model_s *figh_model_t;
  * (round 5 did so for figh_tsqr_selected_wrench / figh_regressor_build_padded without a bump: a library of the older ABI
  * accepts the longer argument list under cdecl and silently ignores the new arguments).  figaroh_plus_amd/_lib.py refuses a
  * library -- in-tree or FIGH_LIB_PATH -- whose figh_version() differs from the value it was written against. */
-#define FIGH_ABI_VERSION 115
+#define FIGH_ABI_VERSION 116
 int figh_version(void);
 const char *figh_last_error(void);
 int figh_device_count(int *count);
@@ -518,6 +518,50 @@ int figh_joint_difference(figh_model_t model, int64_t N, const double *d_q, doub
  * doubles. */
 int figh_gradient_cols(const double *d_F, int64_t rows, int cols, int64_t ld, int ncols_active, double h, const double *d_h,
                        double *d_G, int64_t ldg);
+
+/* ------------------------------------------------------------------ free-flyer real data: orientation filter, wrench transport
+ * The three per-sample Python loops of examples/human/identification.py around the filters and the regressor.  One lane per
+ * sample, fp64, no atomics (two calls give the same bits), compiled without FMA contraction; the operation order is fixed in
+ * the header comment of csrc/figh_freeflyer.hip and repeated element by element by the NumPy mirrors
+ * (identification/identification_tools.py).  Nothing outside [rows, cols) of a padded buffer is written.  Quaternions are
+ * (x y z w), 6-vectors (linear, angular).  All three: N < 1, a leading dimension below the width, a joint id outside the
+ * model, an unknown layout, a NULL pointer or an output that overlaps an input (but see d_out == d_ref below) return
+ * FIGH_ERR_INVALID before anything is launched, figh_last_error says why.
+ *
+ * figh_quat_log: d_rotvec[i, 0:3] = pin.log3(pin.Quaternion(q[i, 3:7])) (examples/human/identification.py:330-339).  d_quat
+ * points at the x of row 0 (q + idx_q + 3 with ld_quat = nq).  The principal rotation vector from the quaternion, not through
+ * a matrix: n = sqrt(x^2 + y^2 + z^2), theta = 2 atan2(n, |w|), r = sgn(w) (theta / n) (x, y, z) with sgn(0) = +1; q and -q
+ * give the same vector; the quaternion is not renormalised (atan2 does not need it).  For n < 2^-13 |w| the series
+ * theta / n = 2 (1 - t^2 / 3 + t^4 / 5) / |w|, t = n / |w|; n = 0 gives three +0.0.  The same function as Pinocchio's, not the
+ * same bits.  Where w changes sign at theta = pi the vector jumps, as the reference's does: it filters the raw vector, and
+ * nothing here unwraps it. */
+int figh_quat_log(const double *d_quat, int64_t N, int64_t ld_quat, double *d_rotvec, int64_t ld_rotvec);
+/* figh_rotvec_to_quat: d_out[i, 0:4] = +-pin.Quaternion(pin.exp3(r_i)) with the sign chosen against d_ref[i, 0:4], the raw
+ * quaternion of the same row (examples/human/identification.py:349-364).  With theta = |r| the canonical quaternion is
+ * q^ = (sin(theta / 2) / theta r, cos(theta / 2)); for theta < 2^-13 the series sin(theta / 2) / theta = 1/2 - theta^2 / 48 +
+ * theta^4 / 3840 and cos(theta / 2) = 1 - theta^2 / 8 + theta^4 / 384.  (1) Eigen's representative sE q^ is what its
+ * matrix-to-quaternion conversion returns for exp3(r): |w^| > 1/2: w > 0; otherwise the vector component of largest
+ * magnitude is positive, the first of equal ones (Eigen's comparisons are strict).  (2) The reference's test: with
+ * d = (sE q^) . ref it keeps the representative when 2 acos(d) < pi / 2 -- here: keep iff d > 0.7071067811865476 -- and negates
+ * it otherwise.  (3) THE ONE DELIBERATE DIFFERENCE: when rounding makes d > 1 the reference's acos is NaN and it negates; here
+ * that case keeps.  Rounding noise decides it, so it cannot be mirrored across math libraries, and -q is the same rotation:
+ * the physical result is unchanged.  d_out may be d_ref itself (same pointer, same leading dimension): a lane reads its row
+ * before it writes it.  Any other overlap is refused. */
+int figh_rotvec_to_quat(const double *d_rotvec, int64_t N, int64_t ld_rotvec, const double *d_ref, int64_t ld_ref,
+                        double *d_out, int64_t ld_out);
+/* figh_wrench_transport: a wrench per sample carried through (R, p) = oMi[joint](q_i), the placement of any joint of the
+ * model.  inverse = 0, pin.Force.se3Action (world <- joint, examples/human/identification.py:471-555): f' = R f,
+ * n' = R n + p x f'.  inverse = 1, se3ActionInverse (joint <- world, :434-453): f' = R^T f, n' = R^T (n - p x f).  d_q: N x nq
+ * sample-major, leading dimension ldq.  Each layout is FIGH_WRENCH_SAMPLE (N x 6, leading dimension 6) or
+ * FIGH_WRENCH_STACKED (component k of sample i at [k N + i]: the order of tau and of figh_regressor_apply).  The support path
+ * of the joint travels by value in the kernel arguments and is walked root first, (R, p) <- (R, p) . placement_j . M_j(q_j)
+ * with the joint model of the regressor kernels (csrc/figh_spatial.h); only the q of the joints on the path is read (the root
+ * free-flyer of the human model: 7 of the 46 doubles of a row).  joint = 0 is the universe (identity).  Both layouts are read
+ * and written with consecutive lanes on consecutive addresses.  FIGH_ERR_UNSUPPORTED (nothing launched): a support path
+ * longer than the kernel arguments hold. */
+enum { FIGH_WRENCH_SAMPLE = 0, FIGH_WRENCH_STACKED = 1 };
+int figh_wrench_transport(figh_model_t model, int joint, int64_t N, const double *d_q, int64_t ldq, const double *d_F,
+                          int layout_in, int inverse, double *d_out, int layout_out);
 
 /* ------------------------------------------------------------------ excitation trajectories
  * The front and the back of the excitation loop: waypoints in, resident (q, v, a) out, constraint vectors out; in between
