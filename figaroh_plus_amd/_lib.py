@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # FIGH_LIB_PATH: another build of the same ABI (same-box A/B of kernel variants); default is the in-tree library
 LIB_PATH = os.environ.get("FIGH_LIB_PATH") or os.path.join(_HERE, "libfigh.so")
 
-ABI_VERSION = 116  # include/figh.h FIGH_ABI_VERSION: load() refuses a library of another ABI
+ABI_VERSION = 117  # include/figh.h FIGH_ABI_VERSION: load() refuses a library of another ABI
 
 FIGH_OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_ALLOC, ERR_UNSUPPORTED, ERR_COMM = -1, -2, -3, -4, -5
@@ -95,6 +95,8 @@ SIGNATURES = {
                                         C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_void_p,
                                         C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     "figh_tsqr_merge_base": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p]),
+    "figh_tsqr_merge_base_norms": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int, C.c_int,
+                                             C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "figh_compact_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_double, C.c_void_p,
                                     C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]),
     "figh_base_permutation": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p]),
@@ -854,6 +856,12 @@ def chain_pass_fused(model, flags, N, d_q, d_v, d_a, d_W, ldw, d_kept, n, d_tau,
 
 def tsqr_merge_base(d_Rs, count, nc, n_free, tol_qr, d_Rk):
     check(load().figh_tsqr_merge_base(d_Rs.ptr, count, nc, n_free, tol_qr, d_Rk.ptr))
+
+
+def tsqr_merge_base_norms(d_Rs, count, nc, n_free, tol_qr, d_part, nblocks, ncols, tol_e, d_colsq, d_sel, d_Rk):
+    """tsqr_merge_base + the sum of the norm partials + select_columns, in one launch where the merge tree allows it."""
+    check(load().figh_tsqr_merge_base_norms(d_Rs.ptr, count, nc, n_free, tol_qr, d_part.ptr, nblocks, ncols, tol_e,
+                                            d_colsq.ptr, d_sel.ptr, d_Rk.ptr))
 
 
 def repack_samples(d_src, N, width):

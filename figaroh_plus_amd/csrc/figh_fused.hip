@@ -561,7 +561,7 @@ static int fused_plan(const figh_model_s *m, int nc, FusedPlan<NJ> *plan) {
 template <int NJ>
 static int launch_fused(const figh_model_s *m, int flags, long N, const double *q, const double *v, const double *a,
                         double *W, const double *tau, const int *d_kept, int n, double *d_colsq, double **Rws_out,
-                        long *count_out) {
+                        long *count_out, const double **part_out, int *nparts_out) {
     using G = FusedGeom<NJ>;
     const int nc = n + (tau ? 1 : 0);
     FusedPlan<NJ> pl;
@@ -577,7 +577,13 @@ static int launch_fused(const figh_model_s *m, int flags, long N, const double *
         FIGH_LAUNCH_TIMED((fused_chain_tsqr_kernel<NJ, false>), dim3((unsigned)grid), dim3(64 * (G::NPROD + ncons)), pl.lds,
                           pl.P, flags, N, q, v, a, W, tau, d_kept, n, nc, part, Rws, ncons, pl.tri, null_pivot_sq());
     }
-    launch_reduce_partials(part, (int)(grid * G::NPROD), G::NC, d_colsq);
+    // (part_out: the caller sums the partials itself -- figh_chain_pass_fused, in its merge launch)
+    if (part_out) {
+        *part_out = part;
+        *nparts_out = (int)(grid * G::NPROD);
+    } else {
+        launch_reduce_partials(part, (int)(grid * G::NPROD), G::NC, d_colsq);
+    }
     FIGH_HIP(hipGetLastError());
     *Rws_out = Rws;
     *count_out = grid * ncons;
@@ -640,7 +646,7 @@ using namespace figh;
 // the checks and the launch of figh_regressor_tsqr_fused / figh_chain_pass_fused
 static int fused_pass_launch(figh_model_t model, int flags, int64_t N, const double *d_q, const double *d_v, const double *d_a,
                              double *d_W, int64_t ldw, double *d_colsq, const int32_t *d_kept, int n, const double *d_tau,
-                             double **Rws, long *count) {
+                             double **Rws, long *count, const double **part = nullptr, int *nparts = nullptr) {
     FIGH_REQUIRE(N >= 0 && n >= 1, "bad shape");
     const DevModel &h = model->host;
     const int nc = n + (d_tau ? 1 : 0);
@@ -655,11 +661,11 @@ static int fused_pass_launch(figh_model_t model, int flags, int64_t N, const dou
     const int f = flags & 7;
     switch (h.nlinks) {
         case 5:
-            return launch_fused<5>(model, f, (long)N, d_q, d_v, d_a, d_W, d_tau, d_kept, n, d_colsq, Rws, count);
+            return launch_fused<5>(model, f, (long)N, d_q, d_v, d_a, d_W, d_tau, d_kept, n, d_colsq, Rws, count, part, nparts);
         case 6:
-            return launch_fused<6>(model, f, (long)N, d_q, d_v, d_a, d_W, d_tau, d_kept, n, d_colsq, Rws, count);
+            return launch_fused<6>(model, f, (long)N, d_q, d_v, d_a, d_W, d_tau, d_kept, n, d_colsq, Rws, count, part, nparts);
         case 7:
-            return launch_fused<7>(model, f, (long)N, d_q, d_v, d_a, d_W, d_tau, d_kept, n, d_colsq, Rws, count);
+            return launch_fused<7>(model, f, (long)N, d_q, d_v, d_a, d_W, d_tau, d_kept, n, d_colsq, Rws, count, part, nparts);
         default:
             // (eight links: two 58 KB tile buffers leave 17 KB of the 160 KB of LDS, less than three consumer triangles)
             set_error("fused regressor + TSQR: serial chains of 5 to 7 joints (LDS: two tile buffers + three consumer triangles)");
@@ -691,17 +697,43 @@ extern "C" int figh_chain_pass_fused(figh_model_t model, int flags, int64_t N, c
     const size_t words = (size_t)ncols + sel_words + (size_t)(nc > 0 ? (nc + 1) * nc : 0);
     FIGH_REQUIRE(n >= 1 && pack_bytes >= sizeof(double) * words, "figh_chain_pass_fused: the pack is [colsq | sel | rows]");
     FIGH_REQUIRE(tail->n == n && (tail->with_tau != 0) == (d_tau != nullptr), "figh_chain_pass_fused: tail of another shape");
-    double *d_colsq = d_pack, *d_rows = d_pack + ncols + sel_words;
-    int32_t *d_sel = reinterpret_cast<int32_t *>(d_pack + ncols);
+    // Where the kernels store the pack: page-locked host memory (figh_host_alloc) has a device address, and the pack is
+    // stored there directly -- nothing is copied, d_pack is not touched.  Pageable memory has none: d_pack, then one copy.
+    double *pack = nullptr;
+    const bool on_host = hipHostGetDevicePointer(reinterpret_cast<void **>(&pack), h_pack, 0) == hipSuccess && pack;
+    if (!on_host) {
+        (void)hipGetLastError();
+        pack = d_pack;
+    }
     double *Rws = nullptr;
+    const double *part = nullptr;
     long count = 0;
-    if (int rc = fused_pass_launch(model, flags, N, d_q, d_v, d_a, d_W, ldw, d_colsq, d_kept, n, d_tau, &Rws, &count)) return rc;
-    // One stream, the order of the separate entries: norms, merge tree, selection, one copy.  (Norms and selection on the
-    // side stream, beside the merge tree, were measured: 10 us less per warm step, but the host's wait then returned on a
-    // 150 us grid during the first forty passes of a process -- profiles/chain_pass_tail_ab.txt.)
-    if (int rc = tsqr_reduce_stack(Rws, count, nc, n, tol_qr, d_rows)) return rc;
-    if (int rc = figh_select_columns(d_colsq, ncols, tol_e, 14, d_sel)) return rc;
-    FIGH_HIP(hipMemcpyAsync(h_pack, d_pack, sizeof(double) * words, hipMemcpyDeviceToHost, stream()));
+    int nparts = 0;
+    if (int rc = fused_pass_launch(model, flags, N, d_q, d_v, d_a, d_W, ldw, d_pack, d_kept, n, d_tau, &Rws, &count, &part, &nparts))
+        return rc;
+    // One stream, two launches: the fused kernel, then the merge launch, which starts when the fused kernel has ended (plain
+    // stream order) and whose last workgroup sums the norms and selects the columns beside the tree -- neither depends on
+    // the other, and nothing on the device waits for another launch.  The end of the merge launch is the end of the pass.
+    StreamEpilogue ep{};
+    ep.part = part;
+    ep.nblocks = nparts;
+    ep.ncols = ncols;
+    ep.tol_e = tol_e;
+    ep.link_stride = 14;
+    ep.colsq = pack;
+    ep.sel = reinterpret_cast<int32_t *>(pack + ncols);
+    ep.rows_on_host = on_host ? 1 : 0;
+    int rc = tsqr_reduce_stack_epilogue(Rws, count, nc, n, tol_qr, pack + ncols + sel_words, ep);
+    if (rc == FIGH_ERR_UNSUPPORTED && on_host) {
+        // the tree is not resident in one launch with that workgroup: the separate steps, through d_pack
+        pack = d_pack;
+        ep.colsq = pack;
+        ep.sel = reinterpret_cast<int32_t *>(pack + ncols);
+        ep.rows_on_host = 0;
+        rc = tsqr_reduce_stack_epilogue(Rws, count, nc, n, tol_qr, pack + ncols + sel_words, ep);
+    }
+    if (rc) return rc;
+    if (pack == d_pack) FIGH_HIP(hipMemcpyAsync(h_pack, d_pack, sizeof(double) * words, hipMemcpyDeviceToHost, stream()));
     FIGH_HIP(hipStreamSynchronize(stream()));
     const int32_t *mask_now = reinterpret_cast<const int32_t *>(h_pack + ncols) + 2 + ncols;
     *changed = 0;

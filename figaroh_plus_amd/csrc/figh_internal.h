@@ -265,7 +265,25 @@ int launch_tsqr_tree(const double *Rs, long count, int nc, int n_free, double to
 // figh_tsqr_stream.hip: the same contract as launch_tsqr_tree, with the levels, the rank decision and the regrouped
 // factorisation software-pipelined (about nc column steps in total).  FIGH_ERR_UNSUPPORTED when the tree does not fit one
 // resident grid.
-int launch_tsqr_stream(const double *Rs, long count, int nc, int n_free, double tol, double *d_out, double *d_rows_out);
+// ep (figh_pass_epilogue.h, needs d_rows_out): one more workgroup sums a pass's norms and selects its columns beside the tree.
+constexpr int kEpilogueMaxCols = 128;  // (serial chains: at most 7 links x 14 columns)
+// What the merge launch does beside its tree when a pass hands it the norms and the selection as well (figh_tsqr_stream.hip,
+// figh_chain_pass_fused).  colsq and sel may be device addresses of page-locked host memory: each word is stored once.
+struct StreamEpilogue {
+    const double *part;  // nblocks x ncols partial sums (nullptr: no epilogue)
+    int nblocks, ncols;  // ncols <= kEpilogueMaxCols
+    double tol_e;
+    int link_stride;
+    double *colsq;       // out: ncols sums
+    int32_t *sel;        // out: 2 + 2 ncols selection words
+    int rows_on_host;    // the launch's rows_out is host memory too: its zero fill is fenced in front of the rows
+};
+int launch_tsqr_stream(const double *Rs, long count, int nc, int n_free, double tol, double *d_out, double *d_rows_out,
+                       const StreamEpilogue *ep = nullptr);
+// figh_linalg.hip: tsqr_reduce_stack (tol_qr >= 0) + the norms and the selection of ep: by that one launch, else by the
+// separate steps (outputs in host memory: FIGH_ERR_UNSUPPORTED instead, with nothing launched)
+int tsqr_reduce_stack_epilogue(const double *d_Rs, long count, int nc, int n_free, double tol_qr, double *d_out,
+                               const StreamEpilogue &ep);
 
 #define FIGH_HIP(expr)                                                                          \
     do {                                                                                        \

@@ -25,6 +25,7 @@
 
 #include "figh_internal.h"
 #include "figh_wave.h"
+#include "figh_pass_epilogue.h"
 #include "figh_tsqr_narrow.h"
 #include "figh_tsqr_narrow_kernel.h"
 
@@ -71,19 +72,13 @@ __global__ __launch_bounds__(256) void colsq_kernel(const double *__restrict__ W
     }
 }
 
-// partial[b][c] -> out[c]: one workgroup per column, strided partial sums + LDS tree (fixed order: deterministic)
+// partial[b][c] -> out[c]: one workgroup per column, strided partial sums + LDS tree (fixed order: deterministic;
+// figh_pass_epilogue.h)
 __global__ __launch_bounds__(256) void reduce_partials_kernel(const double *__restrict__ part, int nblocks, int ncols,
                                                               double *__restrict__ out) {
     __shared__ double sm[256];
     const int c = blockIdx.x;
-    double s = 0.0;
-    for (int b = threadIdx.x; b < nblocks; b += 256) s += part[(long)b * ncols + c];
-    sm[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) sm[threadIdx.x] += sm[threadIdx.x + w];
-        __syncthreads();
-    }
+    reduce_partials_cols(part, nblocks, ncols, c, 1, sm, (int)threadIdx.x);
     if (threadIdx.x == 0) out[c] = sm[0];
 }
 
@@ -211,21 +206,7 @@ __global__ __launch_bounds__(256) void select_columns_kernel(const double *__res
         }
     }
     if (blockIdx.x != 0) return;
-    int total = 0;
-    for (int c = 0; c < ncols; ++c) total += kept[c];
-    for (int c = tid; c < ncols; c += 256) {
-        int pos = 0;
-        for (int e = 0; e < c; ++e) pos += kept[e];
-        // (link_pos: the link-compact layout of figh_regressor_build_padded + FIGH_FLAG_LINK_COMPACT -- a kept column's link
-        // always has a segment there: columns of links without one have norm exactly 0)
-        if (kept[c]) sel[2 + pos] = (link_pos ? max(link_pos[c / 14], 0) : c / 14) * link_stride + c % 14;
-        if (c >= total) sel[2 + c] = 0;
-        sel[2 + ncols + c] = kept[c];
-    }
-    if (tid == 0) {
-        sel[0] = total;
-        sel[1] = ncols;
-    }
+    select_columns_write(kept, ncols, link_stride, link_pos, sel, tid, 256);
 }
 
 // External-wrench regressor of a free-flyer model: in the three FORCE row blocks the six rotational-inertia columns of
@@ -823,6 +804,26 @@ int figh::tsqr_reduce_stack(const double *d_Rs, long count, int nc, int n_free, 
     return reveal_triangle(one, nc, n_free, tol_qr, d_out);
 }
 
+// tsqr_reduce_stack (tol_qr >= 0) with the tail of a pass: ep.part summed into ep.colsq, the columns selected into ep.sel.
+// ONE streamed launch does all three when it takes the stack with one workgroup more (more than one triangle, at most 80
+// columns, a resident tree).  Otherwise the separate steps in the order of the separate entries -- norms, merge levels,
+// selection: same kernels' code, same bits -- unless the outputs are host memory (ep.rows_on_host), which only that
+// launch is meant to write: FIGH_ERR_UNSUPPORTED then, with nothing launched.
+int figh::tsqr_reduce_stack_epilogue(const double *d_Rs, long count, int nc, int n_free, double tol_qr, double *d_out,
+                                     const StreamEpilogue &ep) {
+    if (count > 1 && nc <= 80) {
+        double *one = static_cast<double *>(workspace(sizeof(double) * (size_t)nc * nc, kWsOneTri));
+        if (!one) return FIGH_ERR_ALLOC;
+        const int rc = launch_tsqr_stream(d_Rs, count, nc, n_free, tol_qr, one, d_out, &ep);
+        if (rc != FIGH_ERR_UNSUPPORTED) return rc;
+    }
+    if (ep.rows_on_host) return FIGH_ERR_UNSUPPORTED;
+    launch_reduce_partials(ep.part, ep.nblocks, ep.ncols, ep.colsq);
+    FIGH_HIP(hipGetLastError());
+    if (int rc = tsqr_reduce_stack(d_Rs, count, nc, n_free, tol_qr, d_out)) return rc;
+    return figh_select_columns(ep.colsq, ep.ncols, ep.tol_e, ep.link_stride, ep.sel);
+}
+
 static int tsqr_selected_impl(const double *d_W, int64_t rows, int64_t ldw, const double *d_colsq, int ncols, double tol_e,
                               int link_stride, int nblocks, int n_expected, const double *d_tau, double tol_qr, int32_t *d_sel,
                               double *d_R_out, const int32_t *d_link_pos) {
@@ -1201,6 +1202,24 @@ int figh_tsqr_merge_base(const double *d_Rs, int count, int nc, int n_free, doub
     FIGH_REQUIRE(tol_qr >= 0.0, "tol_qr must be non-negative");
     if (int rc = ensure_device()) return rc;
     return tsqr_reduce_stack(d_Rs, count, nc, n_free, tol_qr, d_Rk_out);
+}
+
+int figh_tsqr_merge_base_norms(const double *d_Rs, int count, int nc, int n_free, double tol_qr, const double *d_part,
+                               int nblocks, int ncols, double tol_e, double *d_colsq, int32_t *d_sel, double *d_rows_out) {
+    FIGH_REQUIRE(d_Rs && d_part && d_colsq && d_sel && d_rows_out, "NULL device pointer");
+    FIGH_REQUIRE(count >= 1 && nc >= 1 && nc <= 512 && n_free >= 1 && n_free <= nc, "bad shape");
+    FIGH_REQUIRE(nblocks >= 1 && ncols >= 1 && ncols <= 1024, "figh_tsqr_merge_base_norms: at least one block, 1 .. 1024 columns");
+    FIGH_REQUIRE(tol_qr >= 0.0, "tol_qr must be non-negative");
+    if (int rc = ensure_device()) return rc;
+    StreamEpilogue ep{};
+    ep.part = d_part;
+    ep.nblocks = nblocks;
+    ep.ncols = ncols;
+    ep.tol_e = tol_e;
+    ep.link_stride = 14;
+    ep.colsq = d_colsq;
+    ep.sel = d_sel;
+    return tsqr_reduce_stack_epilogue(d_Rs, count, nc, n_free, tol_qr, d_rows_out, ep);
 }
 
 }  // extern "C"

@@ -28,6 +28,7 @@
 // columns before it).  Output layout: include/figh.h, figh_tsqr_selected.
 #include "figh_internal.h"
 #include "figh_wave.h"
+#include "figh_pass_epilogue.h"
 
 namespace figh {
 
@@ -326,15 +327,44 @@ __device__ __forceinline__ void solo_stream_panels(double (&T)[solo_tile_n(NCC)]
     if constexpr (P + 1 < NCC) solo_stream_panels<P + 1, NCC>(T, S, c);
 }
 
+// The epilogue workgroup: nthreads / 256 groups take kReduceCols columns each per round.  sm: 256 kReduceCols doubles per
+// group, kept: kEpilogueMaxCols ints (both LDS).
+__device__ __noinline__ void pass_epilogue(const StreamEpilogue ep, double *sm, int *kept, const int tid, const int nthreads) {
+    const int g = tid >> 8, t = tid & 255, ngroups = nthreads >> 8;
+    double *mine = sm + 256 * kReduceCols * g;
+    for (int r0 = 0; r0 < ep.ncols; r0 += kReduceCols * ngroups) {
+        const int c0 = r0 + kReduceCols * g;
+        const int left = ep.ncols - c0;
+        const int count = left < 0 ? 0 : (left < kReduceCols ? left : kReduceCols);
+        reduce_partials_cols(ep.part, ep.nblocks, ep.ncols, c0 < ep.ncols ? c0 : 0, count, mine, t);
+        if (t < count) {
+            const double v = mine[256 * t];
+            ep.colsq[c0 + t] = v;
+            kept[c0 + t] = !(v < ep.tol_e);
+        }
+        __syncthreads();  // the sums are read before the next round overwrites them; kept is complete after the last
+    }
+    select_columns_write(kept, ep.ncols, ep.link_stride, nullptr, ep.sel, tid, nthreads);
+}
+
 // in: plan.nin[0] stacked nc x nc triangles.  sbuf: one poisoned nc x nc triangle per merge workgroup (by blockIdx).
 // out (nullable): the plain triangle.  rows_out (nullable): (nc + 1) x nc, rank decision over the columns k < n_free.
+// ep.part: the launch has one more workgroup behind the regrouping one, which sums a pass's norms and selects its columns
+// (figh_pass_epilogue.h); nobody waits for it and it waits for nobody.
 template <int NCC, int FANR, int NW>
 __global__ __launch_bounds__(64 * NW) void tsqr_stream_kernel(const double *in, double *sbuf, double *out, double *rows_out,
                                                               const StreamPlan plan, const int nc, const int n_free,
-                                                              const double tol) {
+                                                              const double tol, const StreamEpilogue ep) {
     static_assert(NW == 8, "positions are dealt to eight waves");
     constexpr int FAN = 4 * FANR;
     __shared__ double pw[2][NW][16 * NCC];
+    if ((int)blockIdx.x > plan.first[plan.nlevels]) {
+        // ---- the epilogue workgroup (present iff ep.part)
+        __shared__ double esm[(64 * NW / 256) * kReduceCols * 256];
+        __shared__ int ekept[kEpilogueMaxCols];
+        pass_epilogue(ep, esm, ekept, (int)threadIdx.x, 64 * NW);
+        return;
+    }
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane_c = lane & 15, lane_g = lane >> 4;
     const int pad = 16 * NCC - nc;
@@ -382,6 +412,8 @@ __global__ __launch_bounds__(64 * NW) void tsqr_stream_kernel(const double *in, 
     }
     // ---- the regrouping workgroup (present iff rows_out)
     for (int e = threadIdx.x; e < nc * nc; e += 64 * NW) rows_out[e] = 0.0;
+    // (rows in host memory: the zeros have left the compute unit before wave 0 stores a row over them)
+    if (ep.rows_on_host) __threadfence_system();
     __syncthreads();
     if (wave != 0) return;
     SoloCtx c;
@@ -417,7 +449,7 @@ __global__ __launch_bounds__(256) void poison_fill_kernel(double *p, const long 
 
 template <int NCC, int FANR>
 static int launch_stream(const double *Rs, long count, int nc, int n_free, double tol, double *d_out, double *d_rows_out,
-                         int cus) {
+                         int cus, const StreamEpilogue *ep) {
     constexpr int FAN = 4 * FANR;
     StreamPlan plan{};
     int l = 0, total = 0;
@@ -435,8 +467,12 @@ static int launch_stream(const double *Rs, long count, int nc, int n_free, doubl
     }
     plan.nlevels = l;
     plan.first[l] = total;
-    const int grid = total + (d_rows_out ? 1 : 0);
-    // every workgroup must be resident at once (consumers spin on their producers): one 512-thread workgroup per CU
+    // (the epilogue workgroup sits behind the regrouping one: it needs d_rows_out, and a column count its LDS holds)
+    if (ep && (!ep->part || !d_rows_out || ep->ncols < 1 || ep->ncols > kEpilogueMaxCols || ep->nblocks < 0))
+        return FIGH_ERR_UNSUPPORTED;
+    const int grid = total + (d_rows_out ? 1 : 0) + (ep ? 1 : 0);
+    // every workgroup must be resident at once (consumers spin on their producers): one 512-thread workgroup per CU.  The
+    // epilogue workgroup counts: it is the last to be placed, but a tree that only fits without it is not taken
     if (grid > cus || grid < 1 || count * nc * nc >= (1L << 31)) return FIGH_ERR_UNSUPPORTED;
     // the streamed triangles: poisoned when (re)allocated, left poisoned by every launch
     static double *sbuf = nullptr;
@@ -468,18 +504,19 @@ static int launch_stream(const double *Rs, long count, int nc, int n_free, doubl
     }
     if (occ < 1) return FIGH_ERR_UNSUPPORTED;
     hipLaunchKernelGGL((tsqr_stream_kernel<NCC, FANR, 8>), dim3((unsigned)grid), dim3(512), 0, stream(), Rs, sbuf, d_out,
-                       d_rows_out, plan, nc, n_free, tol);
+                       d_rows_out, plan, nc, n_free, tol, ep ? *ep : StreamEpilogue{});
     FIGH_HIP(hipGetLastError());
     return FIGH_OK;
 }
 
-int launch_tsqr_stream(const double *Rs, long count, int nc, int n_free, double tol, double *d_out, double *d_rows_out) {
+int launch_tsqr_stream(const double *Rs, long count, int nc, int n_free, double tol, double *d_out, double *d_rows_out,
+                       const StreamEpilogue *ep) {
     int dev = 0, cus = 256;
     (void)hipGetDevice(&dev);
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
     ProfileScope scope("tsqr_tree");
-    if (nc <= 64) return launch_stream<4, 4>(Rs, count, nc, n_free, tol, d_out, d_rows_out, cus);
-    if (nc <= 80) return launch_stream<5, 2>(Rs, count, nc, n_free, tol, d_out, d_rows_out, cus);
+    if (nc <= 64) return launch_stream<4, 4>(Rs, count, nc, n_free, tol, d_out, d_rows_out, cus, ep);
+    if (nc <= 80) return launch_stream<5, 2>(Rs, count, nc, n_free, tol, d_out, d_rows_out, cus, ep);
     return FIGH_ERR_UNSUPPORTED;
 }
 

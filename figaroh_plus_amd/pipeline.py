@@ -112,7 +112,7 @@ class IdentificationPipeline:
         which ``figh_tsqr_merge`` reduces.  Results are those of the one-shot pass (R is row-order independent)."""
         self.chunk_samples = chunk_samples
         # native_tail: the host tail of problems with at most 80 kept columns runs in libfigh (figh_chain_host_tail), and a
-        # fused pass of a single rank is ONE call (figh_chain_pass_fused: launches, copy, wait, check of the selection, tail).
+        # fused pass of a single rank is ONE call (figh_chain_pass_fused: two launches, wait, check of the selection, tail).
         # False keeps the NumPy / LAPACK tail and one call per launch (tests, A/B runs).
         self.native_tail = bool(native_tail)
         # row_blocks (ACTIVE JOINTS, examples/tiago/identification.py:148-187, :406-424): the dof indices (``act_idxv``) whose
@@ -723,8 +723,9 @@ class IdentificationPipeline:
         return self._finish(rows_k, n, nc, params_r, idx_e, norms.copy(), with_tau, W.rows * ex.world_size, strings)
 
     def _run_fused_native(self, handle, flags, strings, mask, d_kept, n, nc, with_tau):
-        """_run_fused for a single rank in one call (figh_chain_pass_fused): the launches, the copy of the pack, the wait, the
-        check of the selection and the host tail, without a return to Python in between."""
+        """_run_fused for a single rank in one call (figh_chain_pass_fused): the two launches, which store the pack into the
+        page-locked landing buffer themselves, the wait, the check of the selection and the host tail, without a return to
+        Python in between."""
         ex, W = self.exchange, self.W
         ncols = W.ref_cols
         pin = self._landing()
@@ -742,14 +743,7 @@ class IdentificationPipeline:
         self.fused_passes += 1
         self._n_expected = n
         idx_e, params_r = self._kept_lists(mask)
-        out = self._native_out(tail, n, params_r, idx_e, pin.array[:ncols].copy(), with_tau, total_rows, strings)
-        # EMPIRICAL, mechanism not understood (profiles/chain_pass_tail_ab.txt, section 5): during the first forty or so passes of
-        # a process, passes that follow each other without the NumPy / LAPACK tail start on a 149 us grid (steps of 1337 / 1487 /
-        # 1637 us whatever their kernels take).  Entering and leaving the single-thread BLAS context once per pass -- which that
-        # tail did, 8 us -- takes them off the grid; a busy wait of the same or a longer time does not.
-        with _single_threaded_blas(n):
-            pass
-        return out
+        return self._native_out(tail, n, params_r, idx_e, pin.array[:ncols].copy(), with_tau, total_rows, strings)
 
     def _tail_args(self, n, with_tau, total_rows):
         """The argument block of the native host tail for this pass (allocated once per problem shape)."""

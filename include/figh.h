@@ -91,7 +91,7 @@ typedef struct figh_model_s *figh_model_t;
  * (round 5 did so for figh_tsqr_selected_wrench / figh_regressor_build_padded without a bump: a library of the older ABI
  * accepts the longer argument list under cdecl and silently ignores the new arguments).  figaroh_plus_amd/_lib.py refuses a
  * library -- in-tree or FIGH_LIB_PATH -- whose figh_version() differs from the value it was written against. */
-#define FIGH_ABI_VERSION 116
+#define FIGH_ABI_VERSION 117
 int figh_version(void);
 const char *figh_last_error(void);
 int figh_device_count(int *count);
@@ -361,10 +361,12 @@ typedef struct figh_host_tail_s {
 } figh_host_tail_t;
 int figh_chain_host_tail(figh_host_tail_t *tail);
 /* One call for a whole fused pass of a single rank: figh_regressor_tsqr_fused (same arguments, same launches, tol_qr >= 0),
- * figh_select_columns(d_colsq, 14 nlinks, tol_e, 14, d_sel) behind it on the library stream, one copy of the pack to the
- * host, the wait, the check of the selection and figh_chain_host_tail on the staged rows.  d_pack = [colsq (ncols f64) | sel (2 + 2 ncols i32, padded to 8
- * bytes) | rows ((nc + 1) nc f64)], ncols = 14 nlinks: d_colsq, d_sel and d_R_out of the separate entries are its three
- * parts; h_pack (pack_bytes, page-locked: figh_host_alloc) receives it.  h_kept_mask (ncols bytes): the 0 / 1 mask of
+ * figh_select_columns(d_colsq, 14 nlinks, tol_e, 14, d_sel), the pack on the host, the wait, the check of the selection and
+ * figh_chain_host_tail on the staged rows.  Two launches: the merge launch sums the norms and selects the columns beside
+ * its tree (figh_tsqr_merge_base_norms).  The pack = [colsq (ncols f64) | sel (2 + 2 ncols i32, padded to 8 bytes) | rows
+ * ((nc + 1) nc f64)], ncols = 14 nlinks: d_colsq, d_sel and d_R_out of the separate entries are its three parts.  h_pack
+ * (pack_bytes) receives it: page-locked memory (figh_host_alloc) is stored to directly by the kernels -- no copy, d_pack is
+ * left as it is --, any other memory through d_pack and one copy.  h_kept_mask (ncols bytes): the 0 / 1 mask of
  * d_kept.  *changed = 1 when the device's selection is another one: the pass is to be discarded and repeated through
  * figh_regressor_build + figh_tsqr_selected, tail is not touched.  col_norm and sel are bit for bit those of the separate
  * entries (same kernels, same order of the sums).  FIGH_ERR_UNSUPPORTED as for figh_regressor_tsqr_fused. */
@@ -415,6 +417,14 @@ int figh_block_rows_residuals(const double *d_rows, int nblocks, const int32_t *
  * reduction of the all-gathered per-rank triangles): columns k < n_free take part in the rank decision, the others (tau)
  * always count as base columns.  d_rows_out: (nc + 1) x nc. */
 int figh_tsqr_merge_base(const double *d_Rs, int count, int nc, int n_free, double tol_qr, double *d_rows_out);
+/* figh_tsqr_merge_base with the tail of a fused pass: d_part (nblocks x ncols partial sums of diag(W^T W), one row per
+ * producer) is summed over the blocks into d_colsq (ncols) in the library's fixed order, and d_sel (2 + 2 ncols int32) is
+ * figh_select_columns(d_colsq, ncols, tol_e, 14, d_sel).  With more than one triangle, at most 80 columns, ncols <= 128
+ * and a merge tree that is resident in one launch with a workgroup to spare, that launch does all three, the sums and the
+ * selection beside the tree; otherwise they are three steps.  d_colsq, d_sel and d_rows_out are bit for bit the same
+ * either way (one copy of the code, the same order of the sums). */
+int figh_tsqr_merge_base_norms(const double *d_Rs, int count, int nc, int n_free, double tol_qr, const double *d_part,
+                               int nblocks, int ncols, double tol_e, double *d_colsq, int32_t *d_sel, double *d_rows_out);
 
 /* ------------------------------------------------------------------ streamed entry points (W never stored in full)
  * The "fused" forms of SURVEY.md section 8b: the samples are processed in chunks of `chunk_samples` (0 = library
