@@ -10,6 +10,7 @@
 #include <utility>
 #include <vector>
 
+#include "figh_bulk_copy.h"
 #include "figh_internal.h"
 
 namespace figh {
@@ -330,74 +331,24 @@ bool bulk_ready() {
     return true;
 }
 
+// The library stream as the transport of figh::bulk_copy (figh_bulk_copy.h, where the chunk protocol lives).
+struct HipBulkTransport {
+    char *d;
+    char *stage(int i) const { return g_bulk_stage[i]; }
+    int device_to_stage(int i, size_t off, size_t n) { return (int)hipMemcpyAsync(g_bulk_stage[i], d + off, n, hipMemcpyDeviceToHost, g_stream); }
+    int stage_to_device(int i, size_t off, size_t n) { return (int)hipMemcpyAsync(d + off, g_bulk_stage[i], n, hipMemcpyHostToDevice, g_stream); }
+    int record(int i) { return (int)hipEventRecord(g_bulk_ev[i], g_stream); }
+    int wait(int i) { return (int)hipEventSynchronize(g_bulk_ev[i]); }
+    int drain() { return (int)hipStreamSynchronize(g_stream); }
+    void copy(void *dst, const void *src, size_t n) { std::memcpy(dst, src, n); }
+};
+
 // host <-> device in staged chunks; to_host: d -> h, else h -> d.  Returns a hipError_t.
 hipError_t bulk_copy(char *h, char *d, const size_t bytes, const bool to_host) {
-    const long nch = (long)((bytes + kBulkChunk - 1) / kBulkChunk);
     const int nt = (int)std::max(1u, std::min<unsigned>(kBulkThreads, std::thread::hardware_concurrency()));
-    std::atomic<long> go{to_host ? 0 : 2};  // to_host: chunks < go sit in staging; else: chunks < go may be filled
-    std::unique_ptr<std::atomic<int>[]> done(new std::atomic<int>[nch]);  // per chunk: threads that have copied their slice
-    for (long k = 0; k < nch; ++k) done[k].store(0, std::memory_order_relaxed);
-    std::atomic<bool> abort{false};
-    auto span = [&](long k, size_t &lo, size_t &n) { lo = (size_t)k * kBulkChunk; n = std::min(kBulkChunk, bytes - lo); };
-    auto worker = [&](int t) {
-        for (long k = 0; k < nch; ++k) {
-            while (go.load(std::memory_order_acquire) <= k) {
-                if (abort.load(std::memory_order_relaxed)) return;
-                std::this_thread::yield();
-            }
-            size_t lo, n;
-            span(k, lo, n);
-            const size_t per = ((n / nt) + 4095) & ~size_t(4095);
-            const size_t a = std::min(n, per * (size_t)t), b = std::min(n, a + per);
-            if (b > a) {
-                if (to_host) std::memcpy(h + lo + a, g_bulk_stage[k & 1] + a, b - a);
-                else std::memcpy(g_bulk_stage[k & 1] + a, h + lo + a, b - a);
-            }
-            done[k].fetch_add(1, std::memory_order_release);
-        }
-    };
-    std::vector<std::thread> pool;
-    try {
-        for (int t = 0; t < nt; ++t) pool.emplace_back(worker, t);
-    } catch (...) {  // (thread limit of the container: the caller takes the one-piece copy instead)
-        abort.store(true);
-        for (auto &t : pool) t.join();
-        return hipErrorNotReady;
-    }
-    // (per CHUNK: a global count of thread-chunks would let a fast thread's next chunk stand in for a slow thread's current one)
-    auto wait_chunk = [&](long k) { while (done[k].load(std::memory_order_acquire) < nt) std::this_thread::yield(); };
-    hipError_t err = hipSuccess;
-    auto fail = [&](hipError_t e) { if (e != hipSuccess && err == hipSuccess) { err = e; abort.store(true); } return e != hipSuccess; };
-    size_t lo, n;
-    if (to_host) {
-        span(0, lo, n);
-        if (!fail(hipMemcpyAsync(g_bulk_stage[0], d, n, hipMemcpyDeviceToHost, g_stream))) fail(hipEventRecord(g_bulk_ev[0], g_stream));
-        for (long k = 0; k < nch && err == hipSuccess; ++k) {
-            if (k + 1 < nch) {
-                if (k >= 1) wait_chunk(k - 1);  // chunk k - 1 has left the buffer chunk k + 1 lands in
-                span(k + 1, lo, n);
-                if (fail(hipMemcpyAsync(g_bulk_stage[(k + 1) & 1], d + lo, n, hipMemcpyDeviceToHost, g_stream))) break;
-                if (fail(hipEventRecord(g_bulk_ev[(k + 1) & 1], g_stream))) break;
-            }
-            if (fail(hipEventSynchronize(g_bulk_ev[k & 1]))) break;
-            go.store(k + 1, std::memory_order_release);
-        }
-    } else {
-        for (long k = 0; k < nch && err == hipSuccess; ++k) {
-            wait_chunk(k);  // chunk k is in its staging buffer
-            span(k, lo, n);
-            if (fail(hipMemcpyAsync(d + lo, g_bulk_stage[k & 1], n, hipMemcpyHostToDevice, g_stream))) break;
-            if (fail(hipEventRecord(g_bulk_ev[k & 1], g_stream))) break;
-            if (k >= 1) {
-                if (fail(hipEventSynchronize(g_bulk_ev[(k - 1) & 1]))) break;  // chunk k - 1 has left its buffer: chunk k + 1 may be filled
-                go.store(k + 2, std::memory_order_release);
-            }
-        }
-    }
-    if (err != hipSuccess) abort.store(true);
-    for (auto &t : pool) t.join();
-    const hipError_t e2 = hipStreamSynchronize(g_stream);
-    return err != hipSuccess ? err : e2;
+    HipBulkTransport tr{d};
+    const int e = figh::bulk_copy(tr, h, bytes, to_host, kBulkChunk, nt);
+    return e == kBulkNotStarted ? hipErrorNotReady : (hipError_t)e;
 }
 }  // namespace
 

@@ -1562,6 +1562,58 @@ def test_bulk_host_device_copies_roundtrip(lib):
     assert np.array_equal(Gp.numpy(), A)
 
 
+# 24 MB + 4, 32 MB + 32772, 32 MB + 32769: the last chunk's floor(n / 8) is a multiple of 4096 and 8 does not divide n -- the
+# sizes at which the copy threads' shares (csrc/figh_bulk_copy.h: bulk_slice) once left the last n mod 8 bytes to nobody;
+# 32 MB + 32768 is the control on the 8-byte grid
+@pytest.mark.parametrize("nbytes", (25_165_828, 33_587_204, 33_587_201, 33_587_200))
+def test_bulk_copies_move_every_byte_off_the_8_byte_grid(lib, nbytes):
+    """The staged path of figh_memcpy_h2d / figh_memcpy_d2h with byte counts that are no multiple of 8 (uint8; int32 where 4
+    divides the count), each direction alone: the other direction is the plain DMA of a page-locked buffer, so a byte that
+    one direction drops cannot be put back by the other.  Every destination starts as a sentinel the source never holds and
+    has guard bytes behind it, which keep it."""
+    from figaroh_plus_amd.device import host_empty
+    L, S, G = lib.load(), 0xA5, 64
+    src = np.random.default_rng(nbytes).integers(0, S, size=nbytes, dtype=np.uint8)
+    if nbytes % 4 == 0:
+        src = src.view(np.int32)
+    want = src.view(np.uint8)
+    pin = lib.PinnedArray((nbytes + G + 7) // 8)
+    pinned = pin.array.view(np.uint8)[:nbytes + G]
+    d = lib.DeviceArray((nbytes + G,), np.uint8)
+    # host -> device alone: staged upload from pageable memory, plain DMA back into the page-locked buffer
+    lib.check(L.figh_memset(d.ptr, S, nbytes + G))
+    lib.check(L.figh_memcpy_h2d(d.ptr, src.ctypes.data, nbytes))
+    pinned[:] = 0
+    lib.check(L.figh_memcpy_d2h(pinned.ctypes.data, d.ptr, nbytes + G))
+    assert np.array_equal(pinned[:nbytes], want), "h2d: bytes from %d on" % np.flatnonzero(pinned[:nbytes] != want)[0]
+    assert np.all(pinned[nbytes:] == S)
+    # device -> host alone: plain DMA from the page-locked source, staged download into sentinel-filled pageable memory
+    lib.check(L.figh_memset(d.ptr, S, nbytes + G))
+    pinned[:nbytes] = want
+    lib.check(L.figh_memcpy_h2d(d.ptr, pinned.ctypes.data, nbytes))
+    huge = host_empty(8 << 20)  # 64 MB: the huge-page-backed mapping
+    assert huge.base is not None
+    for out in (np.empty(nbytes + G, dtype=np.uint8), huge.view(np.uint8)[:nbytes + G]):
+        out[:] = S
+        lib.check(L.figh_memcpy_d2h(out.ctypes.data, d.ptr, nbytes))
+        assert np.array_equal(out[:nbytes], want), "d2h: bytes from %d on" % np.flatnonzero(out[:nbytes] != want)[0]
+        assert np.all(out[nbytes:] == S)
+    d.free()
+    pin.free()
+
+
+def test_device_array_int32_roundtrip_of_24_mb_plus_one_entry(lib):
+    """An int32 index list of 6 291 457 entries is 24 MB + 4 bytes: DeviceArray.from_host(...).to_host() returns all of it,
+    the last entry included (the one the staged copy dropped in either direction; the destination starts as zeros)."""
+    n = 6_291_457
+    idx = np.arange(1, n + 1, dtype=np.int32)
+    d = lib.DeviceArray.from_host(idx)
+    back = d.to_host(out=np.zeros(n, dtype=np.int32))
+    assert back[-1] == n
+    assert np.array_equal(back, idx)
+    d.free()
+
+
 # ------------------------------------------------------------------------------------------------ two ranks, one GPU
 @pytest.mark.timeout(600)
 def test_two_process_pipeline_on_one_device(lib, golden_ur10, tmp_path):
